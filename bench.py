@@ -12,9 +12,15 @@ the meta-batch is fixed, so scaling is "strong". Inputs are synthetic ERA5-shape
 feature streams (portable numpy seeds 1000+j) resident in HBM before the timed region;
 weights are random-init with the reference's distributions.
 
-At N=1, after the headline timed region (never inside it), the same line also carries
-BASELINE config 4 (``adaptation``: regional fine-tuning, ms per batch-1 sample-step) and one
-rank's share of config 5 (``config5_rank_share``: 8 of the 64 stress tasks, ms per meta-step).
+A plain run sets up, warms up, times the K steps and prints the line. ``--dump-outputs DIR``
+also writes what the last timed meta-step returned (``losses``, ``norms``, ``meta_grad``, ``theta``)
+as ``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared output for output.
+
+With ``--full`` the same line also carries, measured after the headline timed region (never inside
+it): the reference's CPU path (``cpu_baseline``), and at N=1 BASELINE config 4 (``adaptation``:
+regional fine-tuning, ms per batch-1 sample-step) and one rank's share of config 5
+(``config5_rank_share``: 8 of the 64 stress tasks, ms per meta-step); at N>1 the C ABI's own RCCL
+communicator is checked (``collective.capi_comm_check``).
 """
 from __future__ import annotations
 
@@ -51,8 +57,14 @@ def parse():
     p.add_argument("--inner-steps", type=int, default=5)
     p.add_argument("--nodes", type=int, default=441)
     p.add_argument("--order", type=int, default=2, help="2 = second-order MAML (BASELINE config 2)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the extra legs: the CPU baseline, BASELINE config 4 "
+                        "(adaptation), the config-5 rank share and, at N>1, the C-ABI RCCL check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one returned (losses, norms, meta_grad, "
+                        "theta) as DIR/<name>.npy (float32)")
     p.add_argument("--cpu-sample-steps", type=int, default=6,
-                   help="reference-port CPU sample-steps to time (0 = skip)")
+                   help="with --full: reference-port CPU sample-steps to time (0 = skip)")
     p.add_argument("--no-timing", action="store_true", help="disable per-kernel HIP-event timing")
     p.add_argument("--config", type=int, default=2, choices=(2, 5),
                    help="5 = BASELINE stress config: 64 tasks, N=1024 (32x32), Hc=512, LSTM 4x128, K=10, "
@@ -61,10 +73,10 @@ def parse():
     p.add_argument("--dropout", type=float, nargs=2, default=(0.0, 0.0), metavar=("P_GCN", "P_LSTM"),
                    help="train-mode dropout (the reference trains at 0.2 0.2; 0 0 = the parity setting)")
     p.add_argument("--adapt-epochs", type=int, default=2,
-                   help="after the timed region (N=1 only): BASELINE config-4 adaptation epochs to time and "
+                   help="with --full, after the timed region (N=1 only): BASELINE config-4 adaptation epochs to time and "
                         "report under 'adaptation' (0 = skip)")
     p.add_argument("--cfg5-share-tasks", type=int, default=8,
-                   help="after the timed region (N=1, config 2 only): time one second-order meta-step of this "
+                   help="with --full, after the timed region (N=1, config 2 only): time one second-order meta-step of this "
                         "many BASELINE config-5 tasks (8 = one rank's share of the 64 tasks at 8 GPUs) and report "
                         "it under 'config5_rank_share' (0 = skip)")
     p.add_argument("--task-group", default="auto",
@@ -447,6 +459,15 @@ def kernel_report(kern, steps, elapsed, rank_key):
     return out
 
 
+def dump_outputs(out_dir, res, ml):
+    """``--dump-outputs``: what the last timed ``MetaLearner.meta_step`` handed its caller, as float32
+    ``<name>.npy`` files: the step's losses [(K+1), tasks] and pre-clip inner gradient norms [K, tasks] of
+    this rank's tasks, the (all-reduced) meta-gradient and theta after the outer AdamW step."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("losses", res.losses), ("norms", res.norms), ("meta_grad", ml.meta_grad), ("theta", ml.theta)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def relaunch(args) -> int:
     """``--gpus N`` without a torch.distributed launcher: start N ranks (one per GPU) through
     torch.distributed.run as a child process, before this process touches the GPU, and return
@@ -550,7 +571,7 @@ def main():
         dist.all_reduce(q)
         qmse = float(q.item()) / args.tasks
         capi_comm = os.environ.get("SMAML_BENCH_CAPI_COMM", "1")  # 0 = skip, force = also under gloo
-        if (backend == "nccl" and capi_comm != "0") or capi_comm == "force":
+        if args.full and ((backend == "nccl" and capi_comm != "0") or capi_comm == "force"):
             # after the timed region: the C ABI's own RCCL communicator (smaml_comm_*) across
             # the same ranks, on a buffer the size of the meta-step's one all-reduce
             # Its init is bounded by comm_timeout_ms, its collectives are not: run it on a daemon
@@ -622,7 +643,9 @@ def main():
         # min over ranks, and every rank's own elapsed time over the timed region
         out["collective"] = dict(comm, what="one all_reduce(SUM) of [meta-gradient | query-loss sum], "
                                             f"{(ml.theta.numel() + 64) * 4 / 1e6:.2f} MB, per meta-step")
-    if rank == 0 and world == 1 and args.cpu_sample_steps > 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, ml)
+    if args.full and rank == 0 and world == 1 and args.cpu_sample_steps > 0:
         t_step, cores, n_os, n_aff = cpu_baseline(d, args.cpu_sample_steps, P, ei, feats[0])
         sample_steps = args.tasks * (cfg.inner_steps + 1) * cfg.batch
         out["cpu_baseline"] = {
@@ -635,7 +658,7 @@ def main():
                       f"same sample (profiles/r02_cpu_calibration.log)",
         }
         out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
-    if world == 1 and args.adapt_epochs > 0 and args.config == 2:
+    if args.full and world == 1 and args.adapt_epochs > 0 and args.config == 2:
         # BASELINE config 4, after (never inside) the headline timed region, on a fresh context
         ml.ctx.close()
         del ml
@@ -643,7 +666,7 @@ def main():
         progress("config 4 adaptation")
         ad, _ = adaptation_bench(ModelDims(num_nodes=441, hidden_channels=256), P, ei, epochs=args.adapt_epochs)
         out["adaptation"] = ad
-    if world == 1 and args.cfg5_share_tasks > 0 and args.config == 2:
+    if args.full and world == 1 and args.cfg5_share_tasks > 0 and args.config == 2:
         if "ml" in locals():
             ml.ctx.close()
             del ml

@@ -97,7 +97,7 @@ def _comm_main(rank, world, port, out_q):
 def test_capi_rccl_communicator(world):
     """The C ABI's own RCCL communicator (smaml_comm_unique_id / init / allreduce / destroy,
     include/smaml.h) through distributed.capi_comm_check, the collective a non-torch host binds
-    for the outer step (train_hybrid_maml_v5.py:174-179); bench.py runs the same check at every
+    for the outer step (train_hybrid_maml_v5.py:174-179); bench.py --full runs the same check at every
     N>1. RCCL rejects two ranks on one device ("Duplicate GPU detected"), so world 2 needs a box
     with two GPUs; world 1 runs the same id exchange, init, all-reduce and destroy."""
     import torch

@@ -7,7 +7,7 @@
 # session, a failed test run or bench ends it too; nothing is retried):
 #   tests           python -m pytest tests -m gpu (PYTEST_K selects with -k, PYTEST_ARGS adds arguments)
 #   smoke           __graft_entry__.smoke()
-#   bench           python bench.py $BENCH_ARGS          -> gpurun_out/$TAG/bench.log (JSON line last)
+#   bench           python bench.py --full $BENCH_ARGS   -> bench.log in the output directory (JSON line last)
 #   prof            rocprofv3 --kernel-trace --stats of bench.py for one per-rank workload, then separate
 #                   --pmc FETCH_SIZE / WRITE_SIZE passes     -> gpurun_out/$TAG/prof_t$TASKS[_c5]/
 #                   (TASKS, default 15; CONFIG 2 or 5; tools/prof_summary.py reads the directory)
@@ -54,7 +54,7 @@ for s in "$@"; do
       tail -1 "$O/smoke.log"
       ok $rc smoke ;;
     bench)
-      timeout -k 10 900 python bench.py ${BENCH_ARGS:-} > "$O/bench.log" 2>&1
+      timeout -k 10 900 python bench.py --full ${BENCH_ARGS:-} > "$O/bench.log" 2>&1
       rc=$?
       bench_json "$O/bench.log" | cut -c1-400
       ok $rc bench ;;
