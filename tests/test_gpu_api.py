@@ -217,6 +217,66 @@ def test_inner_loop_equals_meta_step_fast_weights():
     assert torch.equal(fa, fb) and torch.equal(la, lb)
 
 
+def test_buffers_grow_in_any_order_bitwise():
+    """Every device buffer a context owns is grown on demand (api.cpp, devbuf.h): a second-order
+    meta-step at 1 task x 2 samples x 1 inner step, then at 2 tasks x 4 samples x 2 inner steps (the
+    workspace, the window table, the second-order stores, the kept features and activations and the
+    weight-image / projection tables all grow), then the first shape again; a GCNConv backward at two row
+    counts, the second larger. No loss buffer is passed, so the context's own grows too. Every output of
+    the first and the third meta-step is bitwise equal, and every call is bitwise equal to the same call
+    on a fresh context."""
+    d = CONFIG1
+    P = synth.init_params(3, d)
+    Ptr, Pg, _ = split(P)
+    gcn = params.pack({k: torch.from_numpy(v) for k, v in Pg.items()}, d, which=1, device=DEV)
+    theta = params.pack({k: torch.from_numpy(v) for k, v in Ptr.items()}, d, device=DEV)
+    streams = [torch.from_numpy(synth.make_features(synth.task_seed(j), d.num_nodes, synth.t_total_for(12))).to(DEV)
+               for j in range(2)]
+    st = _capi.stream_ptr(torch)
+    g = torch.Generator().manual_seed(5)
+    cin, cout = d.input_channels, d.hidden_channels
+    W = torch.randn(cout, cin, generator=g).to(DEV)
+    X = torch.randn(3 * d.num_nodes, cin, generator=g).to(DEV)
+    DZ = torch.randn(3 * d.num_nodes, cout, generator=g).to(DEV)
+
+    def context():
+        ctx = _capi.Context(d, 0)
+        ctx.set_graph(grid_edges(d))
+        ctx.set_gcn_params(gcn)
+        return ctx
+
+    def meta(ctx, Z, B, K):
+        ctx.set_tasks(streams[:Z])
+        mg = torch.zeros_like(theta)
+        norms, fast = torch.zeros(K, Z, device=DEV), torch.zeros(Z, theta.numel(), device=DEV)
+        ctx.meta_step(st, theta, 2, K, B, window_table(MamlConfig(inner_steps=K, batch=B), Z), 0.01, 1.0, 0.5,
+                      meta_grad=mg, norms=norms, fast_out=fast)
+        torch.cuda.synchronize()
+        assert bool(mg.abs().sum() > 0) and bool(torch.isfinite(mg).all())
+        return mg.cpu(), norms.cpu(), fast.cpu()
+
+    def conv_bwd(ctx, rows):
+        dx, dwb = torch.zeros(rows, cin, device=DEV), torch.zeros(cout * cin + cout, device=DEV)
+        ctx.gcn_conv_backward(st, X[:rows].contiguous(), W, DZ[:rows].contiguous(), dx=dx, dwb=dwb)
+        torch.cuda.synchronize()
+        return dx.cpu(), dwb.cpu()
+
+    small, big = (1, 2, 1), (2, 4, 2)
+    ctx = context()
+    m1, m2, m3 = meta(ctx, *small), meta(ctx, *big), meta(ctx, *small)
+    c1, c2, c3 = conv_bwd(ctx, d.num_nodes), conv_bwd(ctx, 3 * d.num_nodes), conv_bwd(ctx, d.num_nodes)
+    ctx.close()
+    fresh = context()
+    f1, fc2, fc1 = meta(fresh, *small), conv_bwd(fresh, 3 * d.num_nodes), conv_bwd(fresh, d.num_nodes)
+    fresh.close()
+    fresh = context()
+    f2 = meta(fresh, *big)
+    fresh.close()
+    for got, want in ((m3, m1), (m1, f1), (m2, f2), (c3, c1), (c1, fc1), (c2, fc2)):
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+
+
 def test_alloc_free_and_world1_comm():
     d = CONFIG1
     ctx = _capi.Context(d, 0)

@@ -2,7 +2,8 @@
 
 api.cpp (dimension checks, parameter layout, the normalised ELL build, argument validation and
 error paths of the C ABI) and the host side of every kernel unit (the launch-plan builders: wavefront
-diagonals, split-K weight-gradient plans and pairs, grid-barrier sizing) are compiled host-only with
+diagonals, split-K weight-gradient plans and pairs, grid-barrier sizing) and the owning type of the
+context's device buffers (``csrc/devbuf.h``, over a host allocator) are compiled host-only with
 ``-fsanitize=address,undefined`` and ``-Werror=missing-field-initializers`` (every plan struct field has
 a default initialiser; no aggregate may leave one out), linked as relocatable device code with the
 driver ``tools/host_sanitize.cpp`` (no device code: nothing launches), and run on the CPU: any

@@ -7,14 +7,19 @@
 // (NULL handles / buffers, no device). Round 5: also the launch-plan builders every kernel launch
 // depends on (kernels.h: the LSTM wavefront diagonals, the split-K weight-gradient plans and their
 // pairing, the grid-barrier sizing), built with -Werror=missing-field-initializers, each plan checked
-// field by field against what was asked for. Exit status 0 = every check passed.
+// field by field against what was asked for. Also the owning type of every device buffer of the context
+// (devbuf.h) over a host allocator: call order, the empty state after a failed grow, the best-effort
+// margin, groups. Exit status 0 = every check passed.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <set>
+#include <string>
 #include <utility>
 #include <vector>
 
+#include "devbuf.h"
 #include "kernels.h"
 #include "smaml.h"
 
@@ -173,11 +178,103 @@ static void check_barrier_grid() {
   CHECK(grid_barrier_grid(1024, 5000, 2) == 2049);  // debug oversize: never co-resident
 }
 
+// A host allocator for DevBuf (csrc/devbuf.h): malloc / free underneath, the calls logged in order
+// ('s' sync, 'f' free, 'a' alloc), a switch that fails the next alloc, a settable free_bytes.
+struct FakeAlloc {
+  static std::string log;
+  static bool fail_next;
+  static int64_t room;
+  static hipError_t alloc(void** p, int64_t bytes) {
+    log += 'a';
+    if (fail_next) {
+      fail_next = false;
+      return hipErrorOutOfMemory;
+    }
+    *p = std::malloc((size_t)bytes);
+    return hipSuccess;
+  }
+  static hipError_t free(void* p) {
+    log += 'f';
+    std::free(p);
+    return hipSuccess;
+  }
+  static hipError_t sync() {
+    log += 's';
+    return hipSuccess;
+  }
+  static int64_t free_bytes() { return room; }
+};
+std::string FakeAlloc::log;
+bool FakeAlloc::fail_next = false;
+int64_t FakeAlloc::room = 0;
+
+// The ownership rule of every device buffer of the context: sync before free, empty after a failure.
+static void check_devbuf() {
+  using Buf = smaml::DevBuf<FakeAlloc>;
+  std::string& log = FakeAlloc::log;
+  {
+    Buf b;
+    CHECK(b.ptr == nullptr && b.cap == 0);
+    CHECK(b.grow(100) == hipSuccess && b.ptr && b.cap == 100 && log == "a");  // nothing to free: no sync
+    std::memset(b.as<char>(), 1, 100);
+    // (a) within capacity: no calls, the same pointer
+    void* p = b.ptr;
+    log.clear();
+    CHECK(b.grow(100) == hipSuccess && b.grow(1) == hipSuccess && b.ptr == p && b.cap == 100 && log.empty());
+    // (b) beyond capacity: sync, free, alloc -- no rounding, no minimum
+    CHECK(b.grow(101) == hipSuccess && b.cap == 101 && log == "sfa");
+    std::memset(b.as<char>(), 2, 101);
+    // (c) a failed grow leaves the buffer empty; a smaller grow allocates afresh; release frees nothing
+    log.clear();
+    FakeAlloc::fail_next = true;
+    CHECK(b.grow(1000) == hipErrorOutOfMemory && b.ptr == nullptr && b.cap == 0 && log == "sfa");
+    log.clear();
+    CHECK(b.release() == hipSuccess && log.empty());
+    CHECK(b.grow(50) == hipSuccess && b.ptr && b.cap == 50 && log == "a");
+    std::memset(b.as<char>(), 3, 50);
+    // (d) grow_if_room: refused at free_bytes <= bytes + margin, a buffer that suffices is kept
+    p = b.ptr;
+    log.clear();
+    FakeAlloc::room = 0;
+    CHECK(b.grow_if_room(50, 1 << 20) && b.ptr == p && b.cap == 50 && log.empty());
+    FakeAlloc::room = 60 + 10;
+    CHECK(!b.grow_if_room(60, 10) && b.ptr == nullptr && b.cap == 0 && log == "sf");  // (not an error: empty)
+    FakeAlloc::room = 60 + 10 + 1;
+    log.clear();
+    CHECK(b.grow_if_room(60, 10) && b.ptr && b.cap == 60 && log == "a");
+    FakeAlloc::fail_next = true;
+    CHECK(!b.grow_if_room(70, 0) && b.ptr == nullptr && b.cap == 0);  // room, but the allocation fails
+    // (e) release twice
+    CHECK(b.grow(8) == hipSuccess);
+    log.clear();
+    CHECK(b.release() == hipSuccess && b.ptr == nullptr && b.cap == 0 && log == "sf");
+    CHECK(b.release() == hipSuccess && log == "sf");
+    // moved-from buffers own nothing (the kept slots live in a vector); the destructor releases
+    CHECK(b.grow(16) == hipSuccess);
+    std::vector<Buf> v;
+    v.push_back(std::move(b));
+    CHECK(b.ptr == nullptr && b.cap == 0 && v[0].cap == 16);
+    log.clear();
+  }
+  CHECK(log == "sf");
+  // a group (the graph's five buffers, the four second-order stores): all grown, or all empty
+  Buf x, y, z;
+  CHECK(smaml::grow_all<FakeAlloc>({{&x, 10}, {&y, 20}, {&z, 30}}) == hipSuccess && x.cap == 10 && y.cap == 20 &&
+        z.cap == 30);
+  CHECK(smaml::grow_all<FakeAlloc>({{&x, 10}, {&y, 20}, {&z, 30}}) == hipSuccess);
+  log.clear();
+  FakeAlloc::fail_next = true;
+  CHECK(smaml::grow_all<FakeAlloc>({{&x, 5}, {&y, 21}, {&z, 30}}) == hipErrorOutOfMemory);
+  CHECK(!x.ptr && !y.ptr && !z.ptr && x.cap == 0 && y.cap == 0 && z.cap == 0 && log == "sfasfsf");
+  CHECK(smaml::grow_all<FakeAlloc>({{&x, 5}, {&y, 21}, {&z, 30}}) == hipSuccess && x.cap == 5);
+}
+
 int main() {
   CHECK(smaml_abi_version() == 7);
   check_waves();
   check_wgrad_plans();
   check_barrier_grid();
+  check_devbuf();
   CHECK(smaml_build_info() != nullptr && std::strlen(smaml_build_info()) > 0);
 
   // ---- parameter layout (hybrid_model.py state_dict order) ----
@@ -272,6 +369,9 @@ int main() {
     CHECK(smaml_set_option(ctx, "no_such_knob", 1) == SMAML_EINVAL);
     CHECK(smaml_set_option(ctx, "keep", -2) == SMAML_EINVAL);
     CHECK(smaml_set_dropout(ctx, 1.5f, 0.f, 0) == SMAML_EINVAL);
+    // a refused graph and a refused reservation leave a context that destroys cleanly
+    CHECK(smaml_set_graph(ctx, badei.data(), 2) == SMAML_EINVAL);
+    CHECK(smaml_reserve(ctx, 1, 1 << 20) == SMAML_EINVAL);
     CHECK(smaml_destroy(ctx) == 0);
   } else {
     CHECK(ctx == nullptr);

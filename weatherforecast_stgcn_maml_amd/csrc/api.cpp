@@ -17,10 +17,12 @@
 #include <thread>
 #include <vector>
 
+#include "devbuf.h"
 #include "kernels.h"
 #include "smaml.h"
 
 using namespace smaml;
+using HipBuf = DevBuf<HipAlloc>;
 
 namespace {
 
@@ -239,27 +241,21 @@ struct smaml_ctx {
   ParamOff po{};
   GcnOff go{};
   int device = 0;
-  int32_t* ell_c = nullptr;
-  float* ell_v = nullptr;
-  // A_hat^T as CSR (GCNConv backward's aggregation of the t = 0 rows; built with the ELL)
-  int32_t *tr_p = nullptr, *tr_c = nullptr;
-  float* tr_v = nullptr;
-  int64_t tr_nnz_cap = 0;
-  float* bw_scratch = nullptr;  // GCNConv backward: [rows][max(cin, cout)] x 2
-  int64_t bw_scratch_cap = 0;
+  // Device memory the context owns is a HipBuf (devbuf.h); every other device pointer here aliases one.
+  // The graph, all five set or none (smaml_set_graph): the normalised ELL (int32 columns, float values)
+  // and A_hat^T as CSR (GCNConv backward's aggregation of the t = 0 rows)
+  HipBuf ell_c, ell_v, tr_p, tr_c, tr_v;
+  HipBuf bw_scratch;  // GCNConv backward: [rows][max(cin, cout)] x 2 floats
   const float* gcn = nullptr;
   // workspace
-  char* arena = nullptr;
-  int64_t arena_bytes = 0;
+  HipBuf arena;
   int zb_cap = 0, z_cap = 0;
   Work w{};
   float* fast = nullptr;
   float* grad = nullptr;
-  float* scratch_loss = nullptr;  // [(steps+1)*Z] fallback when the caller passes no buffer
-  int64_t scratch_loss_cap = 0;
+  HipBuf scratch_loss;  // [(steps+1)*Z] floats, the fallback when the caller passes no buffer
   // device pointer table for sample windows (uploaded through the pinned staging ring)
-  const float** xtab = nullptr;  // never index directly: xtab_at (the table moves when it grows)
-  int64_t xtab_cap = 0;
+  HipBuf xtab;  // never index directly: xtab_at (the table moves when it grows)
   int64_t xtab_n = 0;  // entries of the last upload_xtab
   Staging stage;
   // kernel-variant launch counters and run-time tile knobs (smaml_variant_counts / smaml_set_option)
@@ -274,43 +270,36 @@ struct smaml_ctx {
   // second-order state
   bool so_cap = false;
   float *so_u = nullptr, *so_hu = nullptr;
-  float *so_theta = nullptr, *so_grad = nullptr, *so_norm = nullptr, *so_coef = nullptr;
-  int64_t so_store_cap = 0, so_nc_cap = 0;
-  float* so_F = nullptr;  // [K][Z][T][M][Hc] GCN features of every inner step (null: recompute)
-  int64_t so_F_cap = 0;
+  HipBuf so_theta, so_grad, so_norm, so_coef;  // float; all four set or none (ensure_so_store)
+  HipBuf so_F;  // float [K][Z][T][M][Hc] GCN features of every inner step (empty: recompute)
   std::vector<int8_t> so_fc;  // per inner step: whether run_gcn wrote its so_F slot compact (Work::fcompact)
   float* F_main = nullptr;  // the workspace's own F buffer
   // batch-1 adaptation: GCN features per window of task 0 (the frozen GCN stack without dropout
   // is a pure function of the window, F2), filled on first use and reused by later epochs.
   // Invalidated by smaml_set_graph / _set_gcn_params / _set_tasks.
-  char* gcn_wimg = nullptr;   // pre-split GCN weight images of the fused t >= 1 GCN (kernels_gcn.hip)
-  char* gimg_buf = nullptr;   // pre-split gate-GEMM weight images (prep_gate_images)
-  int64_t gimg_cap = 0;
-  char* bimg_buf = nullptr;   // pre-split BPTT weight images (prep_bwd_images; small-grid BPTT)
-  int64_t bimg_cap = 0;
-  float* xg_buf = nullptr;    // small-grid forward: layer 0's hoisted input projection (run_lstm)
-  int64_t xg_cap = 0;
-  float* xgd_buf = nullptr;   // big-tile forward: layer 0's projection per distinct stream row (prep_xg_dedup)
-  int64_t xgd_cap = 0;
+  HipBuf gcn_wimg;  // pre-split GCN weight images of the fused t >= 1 GCN (kernels_gcn.hip)
+  HipBuf gimg_buf;  // pre-split gate-GEMM weight images (prep_gate_images)
+  HipBuf bimg_buf;  // pre-split BPTT weight images (prep_bwd_images; small-grid BPTT)
+  HipBuf xg_buf;    // small-grid forward: layer 0's hoisted input projection (run_lstm)
+  HipBuf xgd_buf;   // big-tile forward: layer 0's projection per distinct stream row (xgd_scratch)
   // grid-barrier state of the bookkeeping kernels (kernels.h GridBar): device words [3], the pinned
   // device-mapped error flag a timed-out waiter sets, the wait bound and the launch form
-  unsigned* bar = nullptr;
+  HipBuf bar;
   int* bar_err_host = nullptr;
   int* bar_err_dev = nullptr;
   int64_t bar_timeout_us = 4000000;  // smaml_set_option("barrier_timeout_us")
   int bar_fused = 1;                 // smaml_set_option("grid_barrier"): 0 = two launches per kernel
   int bar_oversize = 0;              // smaml_set_option("barrier_oversize"): debug, never co-resident
   uint64_t wall_khz = 0;             // wall_clock64 rate
-  float* ad_F = nullptr;
-  int64_t ad_cap = 0;              // windows the cache holds
-  std::vector<uint8_t> ad_valid;   // per window start
+  HipBuf ad_F;                     // float [ad_valid.size()][T][N][Hc]
+  std::vector<uint8_t> ad_valid;   // per window start the cache has a slot for
   int ad_gcn_batch = 32;           // windows per GCN pass when filling the cache (<= 1: one per step)
   int ad_phase_sync = 0;           // smaml_set_option("adapt_phase_sync"): sync at the phase boundaries
   AdPhases ad_ph;                  // host-timed phases of the last smaml_adapt_steps (smaml_adapt_phases)
   float *Hs_main = nullptr, *Cs_main = nullptr, *Gs_main = nullptr;  // the workspace's own activations
   // primal of the last inner steps kept for the second-order sweep (ensure_keep): slot 0 adds
   // dG + dh to the workspace's Hs/Cs/Gs, slot i >= 1 holds Hs/Cs/Gs/dG/dh of its own
-  std::vector<float*> keep_mem;
+  std::vector<HipBuf> keep_mem;
   int keep_n = 0;
   int64_t keep_rows = 0;  // rows * L the slots were sized for
   int keep_tried_K = -1;
@@ -341,19 +330,23 @@ int ensure_device(smaml_ctx* c) {
   return SMAML_OK;
 }
 
-int free_keep(smaml_ctx* c) {
-  if (c->keep_mem.empty()) return SMAML_OK;
-  HIP_TRY(hipDeviceSynchronize());
-  for (float* p : c->keep_mem) HIP_TRY(hipFree(p));
+// Free HBM that a best-effort buffer must leave beyond its own size (HipBuf::grow_if_room).
+constexpr int64_t SO_F_MARGIN = 4ll << 30, AD_F_MARGIN = 8ll << 30, KEEP_MARGIN = 8ll << 30;
+
+void free_keep(smaml_ctx* c) {
+  if (c->keep_mem.empty()) return;
   c->keep_mem.clear();
   c->keep_n = 0;
   c->keep_rows = 0;
   c->keep_tried_K = -1;
   c->keep_tried_rows = -1;
-  return SMAML_OK;
 }
 
-static void ad_cache_drop(smaml_ctx* c);
+// Drops the adaptation feature cache.
+void ad_cache_drop(smaml_ctx* c) {
+  (void)c->ad_F.release();
+  c->ad_valid.clear();
+}
 
 int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
   const int zb = Z * B;
@@ -410,28 +403,18 @@ int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
   int64_t total = 0;
   for (auto& p : parts) total += (p.second + 255) / 256 * 256;
   c->act_B = -1;
-  TRY(free_keep(c));
-  if (c->arena) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(c->arena));
-    c->arena = nullptr;
-    c->arena_bytes = 0;
-  }
-  char* arena = nullptr;
-  if (hipMalloc((void**)&arena, total) != hipSuccess) {
-    (void)hipGetLastError();
+  free_keep(c);
+  if (c->arena.grow(total) != hipSuccess) {
+    c->zb_cap = c->z_cap = 0;  // no workspace: the next call sizes it afresh
     return fail(SMAML_ENOMEM, "hipMalloc of " + std::to_string(total) + " B workspace failed");
   }
+  char* arena = c->arena.as<char>();
   int64_t off = 0;
   for (auto& p : parts) {
     *p.first = arena + off;
     off += (p.second + 255) / 256 * 256;
   }
   w.wpart_floats = wpart;
-  HIP_TRY(hipMemset(grad, 0, (size_t)zc * c->po.P * 4));
-  HIP_TRY(hipMemset(fast, 0, (size_t)zc * c->po.P * 4));
-  c->arena = arena;
-  c->arena_bytes = total;
   c->w = w;
   c->task_id_dev = task_id_dev;
   c->fast = fast;
@@ -446,6 +429,8 @@ int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
   c->w.dG = w.Gs;
   c->so_u = so_u;
   c->so_hu = so_hu;
+  HIP_TRY(hipMemset(grad, 0, (size_t)zc * c->po.P * 4));
+  HIP_TRY(hipMemset(fast, 0, (size_t)zc * c->po.P * 4));
   if (so_hu) HIP_TRY(hipMemset(so_hu, 0, (size_t)zc * c->po.P * 4));
   return SMAML_OK;
 }
@@ -455,38 +440,9 @@ int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
 int ensure_so_store(smaml_ctx* c, int K, int Z, int B) {
   // GCN features of each inner step, kept for the second-order sweep (weight-independent, F2).
   // Best effort: without room the sweep recomputes them.
-  const int64_t fneed = (int64_t)K * Z * B * c->d.T * c->d.N * c->d.Hc;
-  if (fneed > c->so_F_cap) {
-    if (c->so_F) {
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipFree(c->so_F));
-      c->so_F = nullptr;
-      c->so_F_cap = 0;
-    }
-    size_t freeb = 0, totb = 0;
-    HIP_TRY(hipMemGetInfo(&freeb, &totb));
-    if ((int64_t)freeb > fneed * 4 + (4ll << 30) && hipMalloc((void**)&c->so_F, fneed * 4) == hipSuccess) {
-      c->so_F_cap = fneed;
-    } else {
-      (void)hipGetLastError();
-      c->so_F = nullptr;
-    }
-  }
-  const int64_t need = (int64_t)K * Z * c->po.P;
-  if (need <= c->so_store_cap && (int64_t)K * Z <= c->so_nc_cap) return SMAML_OK;
-  if (c->so_theta) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(c->so_theta));
-    HIP_TRY(hipFree(c->so_grad));
-    HIP_TRY(hipFree(c->so_norm));
-    HIP_TRY(hipFree(c->so_coef));
-  }
-  HIP_TRY(hipMalloc((void**)&c->so_theta, need * 4));
-  HIP_TRY(hipMalloc((void**)&c->so_grad, need * 4));
-  HIP_TRY(hipMalloc((void**)&c->so_norm, (int64_t)K * Z * 4));
-  HIP_TRY(hipMalloc((void**)&c->so_coef, (int64_t)K * Z * 4));
-  c->so_store_cap = need;
-  c->so_nc_cap = (int64_t)K * Z;
+  (void)c->so_F.grow_if_room((int64_t)K * Z * B * c->d.T * c->d.N * c->d.Hc * 4, SO_F_MARGIN);
+  const int64_t nc = (int64_t)K * Z * 4, need = nc * c->po.P;
+  HIP_TRY(grow_all<HipAlloc>({{&c->so_theta, need}, {&c->so_grad, need}, {&c->so_norm, nc}, {&c->so_coef, nc}}));
   return SMAML_OK;
 }
 
@@ -498,7 +454,7 @@ int ensure_so_store(smaml_ctx* c, int K, int Z, int B) {
 // SMAML_KEEP environment variable (0 disables). Needs the GCN feature cache (so_F).
 int ensure_keep(smaml_ctx* c, int K, int Z, int B) {
   const Dims& d = c->d;
-  int want = c->so_F ? K : 0;
+  int want = c->so_F.ptr ? K : 0;
   if (c->keep_max >= 0)
     want = std::min(want, c->keep_max);
   else if (const char* e = std::getenv("SMAML_KEEP"))
@@ -509,20 +465,13 @@ int ensure_keep(smaml_ctx* c, int K, int Z, int B) {
   // already as many as fit for a group at least this large: keep those slots (unequal task groups, e.g.
   // 8 + 7, would otherwise free and re-allocate every slot at every group change, seconds per meta-step)
   if (rowsL <= c->keep_rows && want <= c->keep_tried_K && rowsL <= c->keep_tried_rows) return SMAML_OK;
-  TRY(free_keep(c));
+  free_keep(c);
   c->keep_tried_K = want;
   c->keep_tried_rows = rowsL;
-  const int64_t margin = 8ll << 30;
   for (int i = 0; i < want; ++i) {
-    const int64_t bytes = rowsL * (i == 0 ? 5 : 11) * d.H * 4;  // [dG | dh] or [Hs | Cs | Gs | dG | dh]
-    size_t freeb = 0, totb = 0;
-    HIP_TRY(hipMemGetInfo(&freeb, &totb));
-    float* p = nullptr;
-    if ((int64_t)freeb < bytes + margin || hipMalloc((void**)&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      break;
-    }
-    c->keep_mem.push_back(p);
+    HipBuf slot;  // [dG | dh] or [Hs | Cs | Gs | dG | dh]
+    if (!slot.grow_if_room(rowsL * (i == 0 ? 5 : 11) * d.H * 4, KEEP_MARGIN)) break;
+    c->keep_mem.push_back(std::move(slot));
   }
   c->keep_n = (int)c->keep_mem.size();
   c->keep_rows = rowsL;
@@ -549,10 +498,10 @@ void use_primal(smaml_ctx* c, int slot) {
     w.Hs = c->Hs_main;
     w.Cs = c->Cs_main;
     w.Gs = c->Gs_main;
-    w.dG = c->keep_mem[0];
-    w.dh = c->keep_mem[0] + rowsL * 4 * H;
+    w.dG = c->keep_mem[0].as<float>();
+    w.dh = w.dG + rowsL * 4 * H;
   } else {
-    float* p = c->keep_mem[slot];
+    float* p = c->keep_mem[slot].as<float>();
     w.Hs = p;
     w.Cs = p + rowsL * H;
     w.Gs = p + rowsL * 2 * H;
@@ -581,35 +530,22 @@ void set_step_drop(smaml_ctx* c, int step) {
   c->w.drop = dr;
 }
 
-int ensure_xtab(smaml_ctx* c, int64_t n) {
-  if (n <= c->xtab_cap) return SMAML_OK;
-  if (c->xtab) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree((void*)c->xtab));
-  }
-  const int64_t cap = std::max<int64_t>(n, 1024);
-  c->xtab_n = 0;
-  HIP_TRY(hipMalloc((void**)&c->xtab, cap * sizeof(float*)));
-  c->xtab_cap = cap;
-  return SMAML_OK;
-}
-
 int upload_xtab(smaml_ctx* c, hipStream_t s, const float* const* ptrs, int64_t n) {
-  TRY(ensure_xtab(c, n));
   c->xtab_n = 0;
-  TRY(c->stage.upload(s, (void*)c->xtab, ptrs, n * (int64_t)sizeof(float*)));
+  HIP_TRY(c->xtab.grow(std::max<int64_t>(n, 1024) * (int64_t)sizeof(float*)));
+  TRY(c->stage.upload(s, c->xtab.ptr, ptrs, n * (int64_t)sizeof(float*)));
   c->xtab_n = n;
   return SMAML_OK;
 }
 
 // Device address of entry i of the window table. The only way table pointers are formed: after the
-// upload_xtab that wrote entry i (ensure_xtab may move the table, so a pointer taken before an upload
-// could dangle -- the fault class of round 4's first gcn_dedup run).
+// upload_xtab that wrote entry i (an upload may move the table, so a pointer taken before it could
+// dangle -- the fault class of round 4's first gcn_dedup run).
 int xtab_at(const smaml_ctx* c, int64_t i, const float* const** out) {
-  if (!c->xtab || i < 0 || i >= c->xtab_n)
+  if (i < 0 || i >= c->xtab_n)
     return fail(SMAML_EINVAL, "internal: window-table entry " + std::to_string(i) + " read before its upload (" +
                                   std::to_string(c->xtab_n) + " uploaded)");
-  *out = c->xtab + i;
+  *out = c->xtab.as<const float*>() + i;
   return SMAML_OK;
 }
 
@@ -734,17 +670,7 @@ int join_streams(smaml_ctx* c, hipStream_t s, int n) {
 
 // The XgDedup-row-order scratch (k_xg_dedup tables / k_dg_rowsum sums) with room for `floats`, or null.
 float* xgd_scratch(smaml_ctx* c, int64_t floats) {
-  if (floats > c->xgd_cap) {
-    if (c->xgd_buf) (void)hipFree(c->xgd_buf);
-    c->xgd_buf = nullptr;
-    c->xgd_cap = 0;
-    if (hipMalloc((void**)&c->xgd_buf, floats * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    c->xgd_cap = floats;
-  }
-  return c->xgd_buf;
+  return c->xgd_buf.grow(floats * 4) == hipSuccess ? c->xgd_buf.as<float>() : nullptr;
 }
 
 // Whether this step's layer-0 input-weight gradient runs over distinct stream rows (wgrad_dedup).
@@ -811,26 +737,29 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
   const int zb = w.Z * w.B;
   const float* src = nullptr;
   float* bufs[2] = {w.gcnA, w.gcnB};
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
   if (gcn_mlp_supported(d) && c->kn.gcn_fused) {
-    if (!c->gcn_wimg) HIP_TRY(hipMalloc((void**)&c->gcn_wimg, gcn_wimg_bytes(d)));
+    HIP_TRY(c->gcn_wimg.grow(gcn_wimg_bytes(d)));
+    char* wimg = c->gcn_wimg.as<char>();
     GcnWOff wo;
     for (int k = 0; k < 4; ++k) {
       wo.w[k] = c->go.w[k];
       wo.b[k] = c->go.b[k];
     }
     // the GCN parameters may change between calls (smaml_set_gcn_params keeps the pointer): re-split
-    TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, c->gcn_wimg));
+    TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, wimg));
     const bool dedup = consec && c->kn.gcn_dedup && w.B > 1 && !w.drop.gcn();
     if (dedup) count_variant(w, V_GCN_DEDUP);
     const double rows1 = dedup ? (double)w.Z * (w.B + d.T - 2) * d.N : (double)zb * (d.T - 1) * d.N;
     TIMED(c, s, C_GCN, 2.0 * rows1 * d.Hc * (d.Cin0 + 3.0 * d.Hc),
-          launch_gcn_mlp(s, d, zb, w.B, xtab_dev, c->gcn, wo, c->gcn_wimg, w.F, &w.drop, dedup, w.fcompact));
+          launch_gcn_mlp(s, d, zb, w.B, xtab_dev, c->gcn, wo, wimg, w.F, &w.drop, dedup, w.fcompact));
     for (int k = 0; k < 4; ++k) {  // t = 0 rows: N-row blocks, masks indexed as rows of T*N-row samples
       const bool last = k == 3;
       float* dst = last ? w.F : bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, c->ell_c, c->ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
                              d.N, d.N, &w.drop, rps));
       src = dst;
     }
@@ -844,7 +773,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
       float* dst = bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * w.Z * rpsC * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, w.Z, 1, k == 0 ? first_tab : nullptr, src, dst, false, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, c->ell_c, c->ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
                              rpsC, 0, nullptr));
       src = dst;
     }
@@ -855,7 +784,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
       float* dst = last ? w.F : bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, c->ell_c, c->ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
                              d.N, d.N, &w.drop, rps));
       src = dst;
     }
@@ -867,7 +796,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
     float* dst = last ? w.F : bufs[k & 1];
     TIMED(c, s, C_GCN, 2.0 * zb * rps * c->go.cin[k] * d.Hc,
           launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                           c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, c->ell_c, c->ell_v,
+                           c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
                            rps, d.N, &w.drop));
     src = dst;
   }
@@ -886,21 +815,12 @@ int prep_gate_images(smaml_ctx* c, hipStream_t s, const float* theta, int64_t ts
   if (!c->kn.gate_img || w.drop.lstm()) return SMAML_OK;  // (the dropout kernels load f32 weights)
   GateImgs gi{};
   const int64_t per = gate_img_bytes(d, &gi) * w.Z;
-  const int64_t need = per * (U ? 2 : 1);
-  if (need > c->gimg_cap) {
-    if (c->gimg_buf) HIP_TRY(hipFree(c->gimg_buf));
-    c->gimg_buf = nullptr;
-    c->gimg_cap = 0;
-    if (hipMalloc((void**)&c->gimg_buf, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return SMAML_OK;  // no room: the kernels load and split the f32 weights themselves
-    }
-    c->gimg_cap = need;
-  }
-  gi.th = c->gimg_buf;
+  // no room: the kernels load and split the f32 weights themselves
+  if (c->gimg_buf.grow(per * (U ? 2 : 1)) != hipSuccess) return SMAML_OK;
+  gi.th = c->gimg_buf.as<char>();
   TIMED(c, s, C_MISC, 0, launch_split_gate(s, d, c->po, theta, tstride, w.Z, gi, gi.th));
   if (U) {
-    gi.u = c->gimg_buf + per;
+    gi.u = gi.th + per;
     TIMED(c, s, C_MISC, 0, launch_split_gate(s, d, c->po, U, tstride, w.Z, gi, gi.u));
   }
   w.gimg = gi;
@@ -918,18 +838,9 @@ int prep_bwd_images(smaml_ctx* c, hipStream_t s, const float* theta, int64_t tst
   w.bimg_src = nullptr;
   if (c->kn.small_kw != 2 || !small_kw_ok(d, w) || (int64_t)w.Z * w.M > c->kn.wgrad_group_max_rows) return SMAML_OK;
   BwdImgs bi{};
-  const int64_t need = bwd_img_bytes(d, &bi) * w.Z;
-  if (need > c->bimg_cap) {
-    if (c->bimg_buf) HIP_TRY(hipFree(c->bimg_buf));
-    c->bimg_buf = nullptr;
-    c->bimg_cap = 0;
-    if (hipMalloc((void**)&c->bimg_buf, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return SMAML_OK;  // no room: the BPTT steps load and split the f32 weights themselves
-    }
-    c->bimg_cap = need;
-  }
-  bi.th = c->bimg_buf;
+  // no room: the BPTT steps load and split the f32 weights themselves
+  if (c->bimg_buf.grow(bwd_img_bytes(d, &bi) * w.Z) != hipSuccess) return SMAML_OK;
+  bi.th = c->bimg_buf.as<char>();
   TIMED(c, s, C_MISC, 0, launch_split_bwd(s, d, c->po, theta, tstride, w.Z, bi));
   w.bimg = bi;
   w.bimg_src = theta;
@@ -947,23 +858,13 @@ bool prep_xg_dedup(smaml_ctx* c, hipStream_t s, bool consec, const float* theta,
   w.xgd = XgDedup{};
   if (!consec || !c->kn.xg_dedup || w.B <= 1 || w.drop.gcn() || w.drop.lstm() || (!want_xg && !U)) return false;
   const int64_t per = xg_dedup_rows(w.B, d.T, d.N) * 4 * d.H;
-  const int64_t need = per * w.Z * ((want_xg ? 1 : 0) + (U ? 1 : 0));
-  if (need > c->xgd_cap) {
-    if (c->xgd_buf) HIP_TRY(hipFree(c->xgd_buf));
-    c->xgd_buf = nullptr;
-    c->xgd_cap = 0;
-    if (hipMalloc((void**)&c->xgd_buf, need * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    c->xgd_cap = need;
-  }
+  float* dst = xgd_scratch(c, per * w.Z * ((want_xg ? 1 : 0) + (U ? 1 : 0)));
+  if (!dst) return false;
   XgDedup xd{};
   xd.zstride = per;
   xd.N = d.N;
   w.xgd = xd;  // (zstride read by the launcher)
   const double fl = 2.0 * w.Z * xg_dedup_rows(w.B, d.T, d.N) * 4 * d.H * c->po.lay[0].cin;
-  float* dst = c->xgd_buf;
   if (want_xg) {
     const bool img = w.gimg.th && w.gimg_src == theta;
     TIMED(c, s, C_XG, fl,
@@ -1005,21 +906,13 @@ int run_lstm(smaml_ctx* c, hipStream_t s, const float* theta, int64_t tstride, b
   bool hoist = small_kw_ok(d, w) && (int64_t)w.Z * w.M <= c->kn.wgrad_group_max_rows;
   for (int diag = 0; hoist && diag < d.T; ++diag) hoist = fwd_wave_kw(d, w, c->po, diag);
   if (hoist) {
-    const int64_t per = (int64_t)d.T * w.M * 4 * d.H, need = per * w.Z;
-    if (need > c->xg_cap) {
-      if (c->xg_buf) HIP_TRY(hipFree(c->xg_buf));
-      c->xg_buf = nullptr;
-      c->xg_cap = 0;
-      if (hipMalloc((void**)&c->xg_buf, need * 4) == hipSuccess)
-        c->xg_cap = need;
-      else
-        (void)hipGetLastError();  // no room: the layer-0 steps form the projection themselves
-    }
-    if (c->xg_buf) {
+    const int64_t per = (int64_t)d.T * w.M * 4 * d.H;
+    // (no room: the layer-0 steps form the projection themselves)
+    if (c->xg_buf.grow(per * w.Z * 4) == hipSuccess) {
       TIMED(c, s, C_XG, 2.0 * w.Z * d.T * w.M * 4 * d.H * d.Hc,
             launch_gemm_nt(s, w.F, (int64_t)d.T * w.M * d.Hc, d.T * w.M, d.Hc, theta + c->po.lay[0].wih, tstride,
-                           4 * d.H, c->xg_buf, per, w.Z));
-      w.xg = c->xg_buf;
+                           4 * d.H, c->xg_buf.as<float>(), per, w.Z));
+      w.xg = c->xg_buf.as<float>();
       w.xg_src = theta;
     }
   }
@@ -1053,13 +946,6 @@ int run_lstm(smaml_ctx* c, hipStream_t s, const float* theta, int64_t tstride, b
   w.xgd = XgDedup{};
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
-}
-
-static void ad_cache_drop(smaml_ctx* c) {
-  if (c->ad_F) (void)hipFree(c->ad_F);
-  c->ad_F = nullptr;
-  c->ad_cap = 0;
-  c->ad_valid.clear();
 }
 
 // New graph / GCN parameters / tasks: every cached window is stale, but the slots stay allocated (a
@@ -1296,9 +1182,11 @@ int run_backward_dual(smaml_ctx* c, hipStream_t s, const float* theta, const flo
   return SMAML_OK;
 }
 
+bool graph_set(const smaml_ctx* c) { return c->ell_c.ptr && c->ell_v.ptr; }
+
 int require_ready(smaml_ctx* c) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
-  if (!c->ell_c) return fail(SMAML_ESTATE, "smaml_set_graph not called");
+  if (!graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
   if (!c->gcn) return fail(SMAML_ESTATE, "smaml_set_gcn_params not called");
   return SMAML_OK;
 }
@@ -1307,22 +1195,22 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the bookkeeping kernels' grid-barrier state (zeroed once; self-resetting, see kernels.h GridBar)
 int ensure_bar(smaml_ctx* c) {
-  if (c->bar) return SMAML_OK;
+  if (c->bar.ptr) return SMAML_OK;
   int khz = 0;
   HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
   c->wall_khz = khz > 0 ? (uint64_t)khz : 100000;
   HIP_TRY(hipHostMalloc((void**)&c->bar_err_host, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
   *(volatile int*)c->bar_err_host = 0;
   HIP_TRY(hipHostGetDevicePointer((void**)&c->bar_err_dev, c->bar_err_host, 0));
-  HIP_TRY(hipMalloc((void**)&c->bar, 4 * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->bar, 0, 4 * sizeof(unsigned)));
+  HIP_TRY(c->bar.grow(4 * sizeof(unsigned)));
+  HIP_TRY(hipMemset(c->bar.ptr, 0, 4 * sizeof(unsigned)));
   HIP_TRY(hipDeviceSynchronize());
   return SMAML_OK;
 }
 
 BarPlan bar_plan(const smaml_ctx* c) {
   BarPlan bp{};
-  bp.gb.w = c->bar;
+  bp.gb.w = c->bar.as<unsigned>();
   bp.gb.host_err = c->bar_err_dev;
   bp.gb.timeout = (uint64_t)c->bar_timeout_us * c->wall_khz / 1000;
   bp.fused = c->bar_fused;
@@ -1335,7 +1223,7 @@ BarPlan bar_plan(const smaml_ctx* c) {
 int check_device_error(smaml_ctx* c) {
   if (!c->bar_err_host || *(volatile int*)c->bar_err_host == 0) return SMAML_OK;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemset(c->bar, 0, 4 * sizeof(unsigned)));
+  HIP_TRY(hipMemset(c->bar.ptr, 0, 4 * sizeof(unsigned)));
   HIP_TRY(hipDeviceSynchronize());
   *(volatile int*)c->bar_err_host = 0;
   return fail(SMAML_EHIP,
@@ -1444,41 +1332,19 @@ int smaml_destroy(smaml_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->comm) (void)smaml_comm_destroy(c);
   (void)hipDeviceSynchronize();
-  if (c->arena) (void)hipFree(c->arena);
-  if (c->ell_c) (void)hipFree(c->ell_c);
-  if (c->ell_v) (void)hipFree(c->ell_v);
-  if (c->tr_p) (void)hipFree(c->tr_p);
-  if (c->tr_c) (void)hipFree(c->tr_c);
-  if (c->tr_v) (void)hipFree(c->tr_v);
-  if (c->bw_scratch) (void)hipFree(c->bw_scratch);
-  if (c->xtab) (void)hipFree((void*)c->xtab);
   (void)c->stage.release();
-  if (c->scratch_loss) (void)hipFree(c->scratch_loss);
-  if (c->so_theta) (void)hipFree(c->so_theta);
-  if (c->so_grad) (void)hipFree(c->so_grad);
-  if (c->so_norm) (void)hipFree(c->so_norm);
-  if (c->so_coef) (void)hipFree(c->so_coef);
-  if (c->so_F) (void)hipFree(c->so_F);
-  if (c->gcn_wimg) (void)hipFree(c->gcn_wimg);
-  if (c->gimg_buf) (void)hipFree(c->gimg_buf);
-  if (c->bimg_buf) (void)hipFree(c->bimg_buf);
-  if (c->xg_buf) (void)hipFree(c->xg_buf);
-  if (c->xgd_buf) (void)hipFree(c->xgd_buf);
-  if (c->bar) (void)hipFree(c->bar);
   for (int i = 0; i < 4; ++i) {
     if (c->cs[i]) (void)hipStreamDestroy(c->cs[i]);
     if (c->join_ev[i]) (void)hipEventDestroy(c->join_ev[i]);
   }
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   if (c->bar_err_host) (void)hipHostFree(c->bar_err_host);
-  ad_cache_drop(c);
-  for (float* p : c->keep_mem) (void)hipFree(p);
   for (auto& r : c->tm.recs) {
     (void)hipEventDestroy(r.a);
     (void)hipEventDestroy(r.b);
   }
   for (auto e : c->tm.pool) (void)hipEventDestroy(e);
-  delete c;
+  delete c;  // (every HipBuf releases its memory)
   return SMAML_OK;
 }
 
@@ -1489,13 +1355,6 @@ int smaml_set_graph(smaml_ctx* c, const int64_t* edge_index_host, int64_t num_ed
   std::vector<float> vals;
   TRY(build_ell(edge_index_host, num_edges, c->d.N, cols, vals));
   ad_cache_invalidate(c);
-  if (!c->ell_c) {
-    HIP_TRY(hipMalloc((void**)&c->ell_c, cols.size() * 4));
-    HIP_TRY(hipMalloc((void**)&c->ell_v, vals.size() * 4));
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(c->ell_c, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->ell_v, vals.data(), vals.size() * 4, hipMemcpyHostToDevice));
   // A_hat^T as CSR: entry (t, e) of the ELL (row t gathers column cols[t][e] with weight vals[t][e])
   // becomes row cols[t][e] of the transpose, in ascending t (fixed order)
   const int N = c->d.N;
@@ -1517,18 +1376,16 @@ int smaml_set_graph(smaml_ctx* c, const int64_t* edge_index_host, int64_t num_ed
       tv[pos[j]] = v;
       ++pos[j];
     }
-  if (!c->tr_p) HIP_TRY(hipMalloc((void**)&c->tr_p, (size_t)(N + 1) * 4));
-  if ((int64_t)tc.size() > c->tr_nnz_cap) {
-    if (c->tr_c) HIP_TRY(hipFree(c->tr_c));
-    if (c->tr_v) HIP_TRY(hipFree(c->tr_v));
-    c->tr_nnz_cap = std::max<int64_t>((int64_t)tc.size(), 1);
-    HIP_TRY(hipMalloc((void**)&c->tr_c, c->tr_nnz_cap * 4));
-    HIP_TRY(hipMalloc((void**)&c->tr_v, c->tr_nnz_cap * 4));
-  }
-  HIP_TRY(hipMemcpy(c->tr_p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice));
+  const int64_t ell = (int64_t)cols.size() * 4, nnz = std::max<int64_t>((int64_t)tc.size(), 1) * 4;
+  HIP_TRY(grow_all<HipAlloc>(
+      {{&c->ell_c, ell}, {&c->ell_v, ell}, {&c->tr_p, (int64_t)tp.size() * 4}, {&c->tr_c, nnz}, {&c->tr_v, nnz}}));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(c->ell_c.ptr, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->ell_v.ptr, vals.data(), vals.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->tr_p.ptr, tp.data(), tp.size() * 4, hipMemcpyHostToDevice));
   if (!tc.empty()) {
-    HIP_TRY(hipMemcpy(c->tr_c, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->tr_v, tv.data(), tv.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->tr_c.ptr, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->tr_v.ptr, tv.data(), tv.size() * 4, hipMemcpyHostToDevice));
   }
   return SMAML_OK;
 }
@@ -1547,7 +1404,7 @@ int smaml_reserve(smaml_ctx* c, int32_t tasks, int32_t batch) {
   return reserve(c, tasks, batch);
 }
 
-int64_t smaml_workspace_bytes(const smaml_ctx* c) { return c ? c->arena_bytes : 0; }
+int64_t smaml_workspace_bytes(const smaml_ctx* c) { return c ? c->arena.cap : 0; }
 
 int32_t smaml_so_kept_steps(const smaml_ctx* c) { return c ? c->keep_last : 0; }
 
@@ -1570,15 +1427,15 @@ int smaml_set_task_ids(smaml_ctx* c, const int32_t* ids_host, int32_t n) {
 int smaml_gcn_conv(smaml_ctx* c, void* stream, const float* x, int32_t rows, int32_t cin, const float* weight,
                    const float* bias, int32_t cout, float* out) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
-  if (!c->ell_c) return fail(SMAML_ESTATE, "smaml_set_graph not called");
+  if (!graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
   if (!x || !weight || !bias || !out || rows <= 0 || cin <= 0 || cout <= 0)
     return fail(SMAML_EINVAL, "bad gcn_conv arguments");
   if (cin % 4) return fail(SMAML_EINVAL, "cin must be a multiple of 4");
   if (!aligned16(x) || !aligned16(weight)) return fail(SMAML_EINVAL, "x / weight must be 16-byte aligned");
   TRY(ensure_device(c));
   hipStream_t s = (hipStream_t)stream;
-  launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, false, weight, bias, cin, cout, c->ell_c, c->ell_v,
-                   rows, std::min(rows, c->d.N));
+  launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, false, weight, bias, cin, cout,
+                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, std::min(rows, c->d.N));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1587,7 +1444,7 @@ int smaml_gcn_conv_ex(smaml_ctx* c, void* stream, const float* x, int32_t rows, 
                       const float* bias, int32_t cout, int32_t flags, float* out) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
   const bool plain = (flags & SMAML_GCN_PLAIN) != 0, relu = (flags & SMAML_GCN_RELU) != 0;
-  if (!plain && !c->ell_c) return fail(SMAML_ESTATE, "smaml_set_graph not called");
+  if (!plain && !graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
   if (!x || !weight || !bias || !out || rows <= 0 || cin <= 0 || cout <= 0 || (flags & ~3))
     return fail(SMAML_EINVAL, "bad gcn_conv_ex arguments");
   if (cin % 4) return fail(SMAML_EINVAL, "cin must be a multiple of 4");
@@ -1595,8 +1452,8 @@ int smaml_gcn_conv_ex(smaml_ctx* c, void* stream, const float* x, int32_t rows, 
   TRY(ensure_device(c));
   TRY(check_device_error(c));
   hipStream_t s = (hipStream_t)stream;
-  launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, relu, weight, bias, cin, cout, c->ell_c, c->ell_v, rows,
-                   plain ? 0 : std::min(rows, c->d.N));
+  launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, relu, weight, bias, cin, cout,
+                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, plain ? 0 : std::min(rows, c->d.N));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1605,7 +1462,7 @@ int smaml_gcn_conv_backward(smaml_ctx* c, void* stream, const float* x, int32_t 
                             const float* weight, int32_t cout, const float* dz, int32_t flags, float* dx, float* dwb) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
   const bool plain = (flags & SMAML_GCN_PLAIN) != 0;
-  if (!plain && !c->ell_c) return fail(SMAML_ESTATE, "smaml_set_graph not called");
+  if (!plain && !graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
   if (!x || !weight || !dz || rows <= 0 || cin <= 0 || cout <= 0 || (flags & ~SMAML_GCN_PLAIN) || (!dx && !dwb))
     return fail(SMAML_EINVAL, "bad gcn_conv_backward arguments");
   if (cin % 4 || cout % 4) return fail(SMAML_EINVAL, "cin and cout must be multiples of 4");
@@ -1616,19 +1473,16 @@ int smaml_gcn_conv_backward(smaml_ctx* c, void* stream, const float* x, int32_t 
   TRY(reserve(c, 1, 1));  // the split-K partial slabs of the weight gradient
   hipStream_t s = (hipStream_t)stream;
   const int ng = plain ? 0 : std::min(rows, c->d.N);
-  const int64_t need = 2 * (int64_t)rows * std::max(cin, cout);
-  if (need > c->bw_scratch_cap) {
-    if (c->bw_scratch) HIP_TRY(hipFree(c->bw_scratch));
-    HIP_TRY(hipMalloc((void**)&c->bw_scratch, need * 4));
-    c->bw_scratch_cap = need;
-  }
-  float* t0 = c->bw_scratch;
-  float* t1 = c->bw_scratch + (int64_t)rows * std::max(cin, cout);
+  const int64_t half = (int64_t)rows * std::max(cin, cout);
+  HIP_TRY(c->bw_scratch.grow(2 * half * 4));
+  float* t0 = c->bw_scratch.as<float>();
+  float* t1 = t0 + half;
   if (dwb) {
     // dW = dz^T (A_hat x), db = sum_rows dz: the split-K weight-gradient GEMM with its bias column
     const float* ax = x;
     if (ng > 0) {
-      launch_gather_rows(s, x, t0, rows, cin, ng, c->ell_c, c->ell_v, nullptr, nullptr, nullptr);
+      launch_gather_rows(s, x, t0, rows, cin, ng, c->ell_c.as<int32_t>(), c->ell_v.as<float>(), nullptr, nullptr,
+                         nullptr);
       ax = t0;
     }
     Work w = c->w;
@@ -1642,7 +1496,8 @@ int smaml_gcn_conv_backward(smaml_ctx* c, void* stream, const float* x, int32_t 
     // dx = A_hat^T (dz W): the rows past the graph's nodes see only their self loop
     if (ng > 0) {
       launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, t1);
-      launch_gather_rows(s, t1, dx, rows, cin, ng, nullptr, nullptr, c->tr_p, c->tr_c, c->tr_v);
+      launch_gather_rows(s, t1, dx, rows, cin, ng, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
+                         c->tr_v.as<float>());
     } else {
       launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, dx);
     }
@@ -1760,13 +1615,8 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     if (is_consec[k]) TRY(xtab_at(c, nptr + (int64_t)k * Z, &consec[k]));
   }
   if (!losses) {
-    const int64_t need = (int64_t)(steps + 1) * Z;
-    if (need > c->scratch_loss_cap) {
-      if (c->scratch_loss) HIP_TRY(hipFree(c->scratch_loss));
-      HIP_TRY(hipMalloc((void**)&c->scratch_loss, need * 4));
-      c->scratch_loss_cap = need;
-    }
-    losses = c->scratch_loss;
+    HIP_TRY(c->scratch_loss.grow((int64_t)(steps + 1) * Z * 4));
+    losses = c->scratch_loss.as<float>();
   }
   const int64_t P = c->po.P;
   const float inv = 1.f / ((float)d.N * d.HfC * B);
@@ -1775,13 +1625,16 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   launch_broadcast(s, theta, P, Z, c->fast);
   const double head_fl = 2.0 * Z * c->w.M * d.HfC * d.H;
   const bool so = order == 2;
+  float *const so_theta = c->so_theta.as<float>(), *const so_grad = c->so_grad.as<float>();
+  float *const so_norm = c->so_norm.as<float>(), *const so_coef = c->so_coef.as<float>();
+  float* const so_F = c->so_F.as<float>();
   if (so) c->so_fc.assign((size_t)steps, 0);
   for (int k = 0; k < steps; ++k) {
     const float* const* xt = xstep[k];
     if (dropout) set_step_drop(c, k);
     if (so) {
-      HIP_TRY(hipMemcpyAsync(c->so_theta + (int64_t)k * Z * P, c->fast, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
-      c->w.F = c->so_F ? c->so_F + (int64_t)k * Z * B * d.T * d.N * d.Hc : c->F_main;
+      HIP_TRY(hipMemcpyAsync(so_theta + (int64_t)k * Z * P, c->fast, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
+      c->w.F = so_F ? so_F + (int64_t)k * Z * B * d.T * d.N * d.Hc : c->F_main;
     }
     const int slot = steps - 1 - k;
     use_primal(c, slot < nkeep ? slot : SET_MAIN);
@@ -1792,12 +1645,12 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     TRY(run_backward(c, s, c->fast, P, c->grad));
     // the inner SGD step (clip_grad_norm_ + SGD) of every task: one kernel
     if (so) {
-      HIP_TRY(hipMemcpyAsync(c->so_grad + (int64_t)k * Z * P, c->grad, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(so_grad + (int64_t)k * Z * P, c->grad, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
       TIMED(c, s, C_MISC, 0,
             HIP_TRY(launch_inner_sgd(s, c->fast, c->grad, P, Z, c->w.sqpart, inner_lr, max_norm,
-                                     c->so_norm + (int64_t)k * Z, c->so_coef + (int64_t)k * Z, bar_plan(c))));
+                                     so_norm + (int64_t)k * Z, so_coef + (int64_t)k * Z, bar_plan(c))));
       if (norms)
-        HIP_TRY(hipMemcpyAsync(norms + (int64_t)k * Z, c->so_norm + (int64_t)k * Z, Z * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(norms + (int64_t)k * Z, so_norm + (int64_t)k * Z, Z * 4, hipMemcpyDeviceToDevice, s));
     } else {
       TIMED(c, s, C_MISC, 0,
             HIP_TRY(launch_inner_sgd(s, c->fast, c->grad, P, Z, c->w.sqpart, inner_lr, max_norm,
@@ -1826,26 +1679,26 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     // w_{K-1}: the clip-adjusted direction of the last inner step at v_K (one kernel: dot + direction)
     if (steps > 0)
       TIMED(c, s, C_MISC, 0,
-            HIP_TRY(launch_sweep_update(s, V, nullptr, 0.f, c->so_grad + (int64_t)(steps - 1) * Z * P, P, Z,
-                                        c->w.sqpart, c->so_norm + (int64_t)(steps - 1) * Z,
-                                        c->so_coef + (int64_t)(steps - 1) * Z, max_norm, c->so_u,
+            HIP_TRY(launch_sweep_update(s, V, nullptr, 0.f, so_grad + (int64_t)(steps - 1) * Z * P, P, Z,
+                                        c->w.sqpart, so_norm + (int64_t)(steps - 1) * Z,
+                                        so_coef + (int64_t)(steps - 1) * Z, max_norm, c->so_u,
                                         bar_plan(c))));
     for (int k = steps - 1; k >= 0; --k) {
-      const float* th = c->so_theta + (int64_t)k * Z * P;
+      const float* th = so_theta + (int64_t)k * Z * P;
       const float* const* xt = xstep[k];
-      c->w.F = c->so_F ? c->so_F + (int64_t)k * Z * B * d.T * d.N * d.Hc : c->F_main;
+      c->w.F = so_F ? so_F + (int64_t)k * Z * B * d.T * d.N * d.Hc : c->F_main;
       const int slot = steps - 1 - k;
       use_primal(c, slot < nkeep ? slot : SET_MAIN);
       c->w.primal_kept = slot < nkeep ? 1 : 0;
       if (dropout) set_step_drop(c, k);  // the masks of inner step k's forward
-      TRY(run_forward_dual(c, s, th, c->so_u, P, xt, c->so_F != nullptr, consec[k], c->so_fc[k]));
+      TRY(run_forward_dual(c, s, th, c->so_u, P, xt, so_F != nullptr, consec[k], c->so_fc[k]));
       TIMED(c, s, C_HEAD, 3.0 * head_fl, launch_head_dual(s, d, c->w, th, c->so_u, P, c->po, xt, 2.f * inv));
       TRY(run_backward_dual(c, s, th, c->so_u, P, c->so_hu));
       if (k > 0)  // v_k = v_{k+1} - lr H_k w_k and w_{k-1} (dot g_{k-1} . v_k, direction): one kernel
         TIMED(c, s, C_MISC, 0,
-              HIP_TRY(launch_sweep_update(s, V, c->so_hu, -inner_lr, c->so_grad + (int64_t)(k - 1) * Z * P, P, Z,
-                                          c->w.sqpart, c->so_norm + (int64_t)(k - 1) * Z,
-                                          c->so_coef + (int64_t)(k - 1) * Z, max_norm, c->so_u,
+              HIP_TRY(launch_sweep_update(s, V, c->so_hu, -inner_lr, so_grad + (int64_t)(k - 1) * Z * P, P, Z,
+                                          c->w.sqpart, so_norm + (int64_t)(k - 1) * Z,
+                                          so_coef + (int64_t)(k - 1) * Z, max_norm, c->so_u,
                                           bar_plan(c))));
       else
         TIMED(c, s, C_MISC, 0, launch_axpy(s, V, c->so_hu, (int64_t)Z * P, -inner_lr));
@@ -1882,7 +1735,7 @@ static int ad_cache_fill(smaml_ctx* c, hipStream_t s, const int32_t* windows, in
     size_t j = i + 1;
     while (j < need.size() && need[j] == need[j - 1] + 1 && (int)(j - i) < c->ad_gcn_batch) ++j;
     set_work(c, (int)(j - i), 1);
-    c->w.F = c->ad_F + (int64_t)need[i] * fsz;
+    c->w.F = c->ad_F.as<float>() + (int64_t)need[i] * fsz;
     const float* const* xt = nullptr;
     TRY(xtab_at(c, (int64_t)i, &xt));
     TRY(run_gcn(c, s, xt));
@@ -1903,36 +1756,30 @@ static int ad_prepare(smaml_ctx* c, hipStream_t s, int B, bool* cache_out) {
   const Dims& d = c->d;
   auto t0 = clk::now();
   const bool fill_batched = B == 1 && !(c->p_gcn > 0.f) && c->ad_gcn_batch > 1;
-  const int64_t had = c->arena_bytes;
+  const int64_t had = c->arena.cap;
   // (the cache fill's GCN passes run ad_gcn_batch windows as tasks: size the workspace for them
   // first, since a growing workspace drops the cache)
   TRY(reserve(c, fill_batched ? c->ad_gcn_batch : 1, B));
-  if (c->arena_bytes != had) {
-    HIP_TRY(hipMemsetAsync(c->arena, 0, (size_t)c->arena_bytes, s));
+  if (c->arena.cap != had) {
+    HIP_TRY(hipMemsetAsync(c->arena.ptr, 0, (size_t)c->arena.cap, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   auto t1 = clk::now();
   const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
   const int64_t n = c->t_total.empty() ? 0 : c->t_total[0];
   bool cache = B == 1 && !(c->p_gcn > 0.f) && n > 0;
-  if (cache && c->ad_F && c->ad_cap < n) ad_cache_drop(c);  // a longer stream than the cache was sized for
-  if (cache && !c->ad_F) {
-    size_t freeb = 0, totb = 0;
-    HIP_TRY(hipMemGetInfo(&freeb, &totb));
-    if ((int64_t)freeb > n * fsz * 4 + (8ll << 30) && hipMalloc((void**)&c->ad_F, (size_t)(n * fsz * 4)) == hipSuccess) {
-      c->ad_cap = n;
+  if (cache && (int64_t)c->ad_valid.size() < n) {  // no cache yet, or a longer stream than it was sized for
+    ad_cache_drop(c);
+    if (c->ad_F.grow_if_room(n * fsz * 4, AD_F_MARGIN)) {
       c->ad_valid.assign((size_t)n, 0);
-      HIP_TRY(hipMemsetAsync(c->ad_F, 0, (size_t)(n * fsz * 4), s));
+      HIP_TRY(hipMemsetAsync(c->ad_F.ptr, 0, (size_t)(n * fsz * 4), s));
       HIP_TRY(hipStreamSynchronize(s));
-    } else {
-      (void)hipGetLastError();
-      c->ad_F = nullptr;
     }
   }
   auto t2 = clk::now();
   c->ad_ph.ms[AD_RESERVE] += std::chrono::duration<double, std::milli>(t1 - t0).count();
   c->ad_ph.ms[AD_ALLOC] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-  *cache_out = cache && c->ad_F;
+  *cache_out = cache && c->ad_F.ptr;
   return SMAML_OK;
 }
 
@@ -1989,7 +1836,7 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
     if (dropout) set_step_drop(c, step0 + k);
     if (cache) {
       const int wv = windows_host[k];
-      c->w.F = c->ad_F + (int64_t)wv * fsz;
+      c->w.F = c->ad_F.as<float>() + (int64_t)wv * fsz;
       if (!c->ad_valid[wv]) {
         TRY(run_gcn(c, s, xt));  // writes the window's features straight into its cache slot
         c->ad_valid[wv] = 1;
