@@ -147,6 +147,35 @@ int smaml_forward(smaml_ctx* ctx, void* stream, const float* theta, const float*
 int smaml_set_tasks(smaml_ctx* ctx, int32_t ntasks, const float* const* features_host,
                     const int32_t* t_total_host);
 
+/* Rolling forecast over a registered stream: what validate_hybrid_v5.validateAdapted's no-grad forward
+ * (validate_hybrid_v5.py:189-237) and adaptModel's validation loop (adapt_hybrid_v5.py:216-231) compute,
+ * for any number of windows and, without `skill`, past the end of the stream. Runs the `nwin` windows
+ * (starts windows_host[i]) of task `task` of smaml_set_tasks in passes of at most `batch` windows with
+ * theta (one flat trainable vector), in eval mode (smaml_set_dropout does not apply).
+ *   A window needs w >= 0 and w + T <= t_total (its inputs); with `skill` also w + T + Hf < t_total (its
+ *   targets): otherwise SMAML_EINVAL naming the window. pred and skill both NULL: SMAML_EINVAL.
+ *   pred (device, optional) [nwin][N*Hf][C]: normalised predictions, rows n*Hf + h as smaml_forward.
+ *   skill (device doubles, optional) [3][Hf][C], overwritten: per target lead h' and variable c, over all
+ *   windows and nodes, with the F4 pairing of the training loss (flat prediction row r = n*Hf + h is
+ *   compared with target (h' = r / N, n' = r % N)):
+ *     [0] sum (s_c (p - y))^2, [1] sum |s_c (p - y)|, [2] sum (s_c (y_last - y))^2 (persistence),
+ *   y = stream[w+T+1+h', n', c], y_last = stream[w+T-1, n', c], s_c = scale_host[c] (NULL = 1; e.g. the
+ *   adaptation checkpoint's std, giving physical units -- the mean cancels). Fixed-order sums (f32 per
+ *   block, double across blocks and passes): bitwise repeatable.
+ * The LSTM runs an inference-only step (k_lstm_fwd_infer) that keeps h and c of the two most recent
+ * steps per layer instead of the activations a backward needs. A pass of consecutive windows
+ * (w[b] = w[0] + b, more than one) computes the GCN features and layer 0's input projection once per
+ * distinct stream row (options gcn_dedup / xg_dedup / f_compact); other passes compute per window.
+ * Buffers are the forecast's own, sized from the pass size (they grow, never shrink; smaml_forecast_bytes):
+ * the call does not go through smaml_reserve, leaves smaml_workspace_bytes, the adaptation feature cache
+ * and the state of smaml_meta_step alone, and a pending smaml_forward / smaml_backward (or smaml_lstm_
+ * forward / _backward) pair STAYS VALID across it: the backward may follow a forecast. */
+int smaml_forecast(smaml_ctx* ctx, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
+                   int32_t nwin, int32_t batch, const float* scale_host, float* pred, double* skill);
+
+/* Bytes of device memory the forecast's own buffers hold (not part of smaml_workspace_bytes). */
+int64_t smaml_forecast_bytes(const smaml_ctx* ctx);
+
 /* One meta-step over all registered tasks (meta_update_v4, train_hybrid_maml_v5.py:144-184,
  * wrapping inner_loop_v4, :110-141):
  *   per task: fast = theta; for k < steps: B-sample support step (mean MSE, backward,
@@ -278,7 +307,8 @@ int smaml_comm_destroy(smaml_ctx* ctx);
 int smaml_timing(smaml_ctx* ctx, int32_t enable);
 
 /* Synchronise, then report and reset per category: summed kernel milliseconds, summed
- * algorithmic FLOPs, launch counts. One kernel symbol per category (index): 0 gcn_layer,
+ * algorithmic FLOPs, launch counts (smaml_forecast's launches count under gcn_layer, xg_proj,
+ * lstm_fwd_step, head_loss and misc). One kernel symbol per category (index): 0 gcn_layer,
  * 1 lstm_fwd_step, 2 lstm_fwd_dual, 3 head_loss, 4 head_dh, 5 lstm_bwd_step, 6 lstm_bwd_dual,
  * 7 wgrad (split-K GEMM), 8 wgrad_reduce, 9 misc, 10 xg_proj (layer 0's input projection formed before
  * the wavefront: k_xg_dedup once per distinct stream row of consecutive windows, or the batch-1
@@ -293,7 +323,7 @@ int smaml_timing_collect(smaml_ctx* ctx, double* ms, double* flops, int64_t* cou
  * kernels.h enum Variant (_capi.VARIANTS): fwd, fwd_drop, fwd_split, fwd_img, fwd_dual,
  * fwd_dual_kept, fwd_dual_img, bwd_big, bwd_small, bwd_split, bwd_dual_big, bwd_dual_big_kept,
  * bwd_dual_small, bwd_dual_small_kept, wgrad, wgrad_wide, wgrad_pair, fwd_kw, bwd_kw, gcn_dedup,
- * xg_dedup, wgrad_dedup, f_compact.
+ * xg_dedup, wgrad_dedup, f_compact, fwd_infer (smaml_forecast's inference step).
  * Writes min(cap, count) entries, *count = number of variants; reset != 0 zeroes them. Host-side
  * counters: no synchronisation. Lets tests assert which configurations ran. */
 int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count, int32_t reset);

@@ -1,0 +1,134 @@
+"""Rolling forecast (smaml_forecast) against the training-forward way of scoring the same windows, timed
+on one MI355X: config-2 dims, one region of N = 441 nodes, the reference's 1,200-window cap
+(adapt_hybrid_v5.py:152), consecutive windows.
+
+Arms, alternating in one process, each repetition timed on the host with a device synchronise inside:
+  forecast_32 / forecast_128  ctx.forecast(skill sums only) in passes of 32 / 128 windows
+  meta_step_32                the yardstick: adapt.evaluate's loop of smaml_meta_step(order=0, steps=0,
+                              batch=32) over the same windows, one scalar MSE per pass
+The forecast arms run on one context, the yardstick on another (their buffers are reported apart). After
+the timed repetitions one more repetition per arm runs with the per-category event timing on
+(smaml_timing_collect), outside the timed region.
+
+Prints the arms' median and min-max, windows/s, the ratio to the yardstick, smaml_forecast_bytes against
+smaml_workspace_bytes, the per-category kernel times, and ONE JSON line last.
+
+Usage: python tools/bench_forecast.py [--reps 5] [--warmup 1] [--windows 1200]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--reps", type=int, default=5, help="timed repetitions per arm (>= 5 for the spread)")
+    p.add_argument("--warmup", type=int, default=1, help="untimed repetitions per arm first")
+    p.add_argument("--windows", type=int, default=1200)
+    a = p.parse_args()
+    import torch
+
+    from weatherforecast_stgcn_maml_amd import _capi, adapt, params, synth
+    from weatherforecast_stgcn_maml_amd.config import SEED, ModelDims
+    from weatherforecast_stgcn_maml_amd.graph import build_spatial_graph
+
+    d = ModelDims(num_nodes=441, hidden_channels=256)
+    lats, lons = synth.region_grid(n_lat=21, n_lon=21)
+    ei, _, _ = build_spatial_graph(lats, lons, 4)
+    P = synth.init_params(SEED, d)
+    names = [k for k in P if k.startswith(("lstm.", "output_layer."))]
+    dev = torch.device("cuda:0")
+    gflat = params.pack({k: v for k, v in P.items() if k not in names}, d, which=1, device=dev)
+    theta = params.pack({k: P[k] for k in names}, d, which=0, device=dev)
+    t_total = a.windows + d.window_size + d.forecast_horizon
+    stream_t = torch.from_numpy(synth.make_features(synth.task_seed(0), d.num_nodes, t_total)).to(dev)
+    windows = list(range(a.windows))
+    st = _capi.stream_ptr(torch)
+
+    def context():
+        ctx = _capi.Context(d, 0)
+        ctx.set_graph(ei)
+        ctx.set_gcn_params(gflat)
+        ctx.set_tasks([stream_t])
+        return ctx
+
+    fc_ctx, ms_ctx = context(), context()
+    sums = torch.zeros(3, d.forecast_horizon, d.output_channels, device=dev, dtype=torch.float64)
+    out = {}
+
+    def forecast_arm(batch):
+        def run():
+            fc_ctx.forecast(st, theta, windows, batch, skill=sums)
+            torch.cuda.synchronize()
+            out[f"forecast_{batch}"] = float(sums[0].sum().item()) / (a.windows * d.num_nodes * d.head_out)
+        return run
+
+    def meta_arm():
+        out["meta_step_32"] = adapt.evaluate(ms_ctx, theta, windows, 32)  # (each pass ends with loss.item(): a sync)
+        torch.cuda.synchronize()
+
+    arms = {"forecast_32": (forecast_arm(32), fc_ctx), "forecast_128": (forecast_arm(128), fc_ctx),
+            "meta_step_32": (meta_arm, ms_ctx)}
+    times = {k: [] for k in arms}
+    arms["forecast_32"][0]()  # (untimed) the forecast's buffers at pass size 32, before the 128-window passes grow them
+    fb32 = fc_ctx.forecast_bytes()
+    for _ in range(a.warmup):
+        for fn, _ in arms.values():
+            fn()
+    for _ in range(a.reps):
+        for k, (fn, _) in arms.items():  # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    cats = {}
+    for k, (fn, ctx) in arms.items():  # where the time goes: one more repetition with event timing on
+        ctx.timing(True)
+        ctx.timing_collect()
+        fn()
+        cats[k] = {c: v for c, v in ctx.timing_collect().items() if v["launches"]}
+        ctx.timing(False)
+
+    # the same quantity from both paths: the mean squared error over the windows (unscaled)
+    assert np.isfinite(list(out.values())).all(), out
+    assert abs(out["forecast_32"] - out["meta_step_32"]) <= 1e-4 * out["meta_step_32"], out
+    res = {}
+    for k, ts in times.items():
+        ms = np.asarray(ts) * 1e3
+        res[k] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()),
+                  "windows_per_s": a.windows / float(np.median(ts))}
+        print(f"{k:13s} median {res[k]['median_ms']:8.1f} ms  (min {res[k]['min_ms']:.1f} - max {res[k]['max_ms']:.1f}, "
+              f"{a.reps} reps)  {res[k]['windows_per_s']:8.0f} windows/s  mse {out[k]:.6f}")
+    base = res["meta_step_32"]
+    for k in ("forecast_32", "forecast_128"):
+        res[k]["vs_meta_step_32"] = base["median_ms"] / res[k]["median_ms"]
+        inside = res[k]["median_ms"] <= base["max_ms"]
+        print(f"{k}: {res[k]['vs_meta_step_32']:.2f}x the yardstick's median; median "
+              f"{'within or below' if inside else 'ABOVE'} the yardstick's max ({base['max_ms']:.1f} ms); "
+              f"ranges {'overlap' if res[k]['max_ms'] >= base['min_ms'] else 'do not overlap'}")
+    fb, wb = fc_ctx.forecast_bytes(), ms_ctx.workspace_bytes()
+    print(f"smaml_forecast_bytes {fb32} ({fb32 / 2**20:.0f} MiB) at pass size 32, {fb} ({fb / 2**20:.0f} MiB) after "
+          f"the passes of 128 (workspace of that context: {fc_ctx.workspace_bytes()} B); smaml_workspace_bytes of the "
+          f"yardstick {wb} ({wb / 2**20:.0f} MiB, batch 32): ratio {fb32 / wb:.3f} at equal pass size")
+    for k, c in cats.items():
+        print(f"{k} kernel ms by category: " +
+              ", ".join(f"{n} {v['ms']:.1f} ({v['launches']})" for n, v in c.items()))
+    print(json.dumps({
+        "metric": "rolling forecast + skill sums, windows/sec (N=441, T=24, config-2 dims)",
+        "value": res["forecast_32"]["windows_per_s"], "unit": "windows/s", "higher_is_better": True,
+        "windows": a.windows, "reps": a.reps, "warmup": a.warmup, "arms": res,
+        "forecast_bytes_pass32": fb32, "forecast_bytes": fb, "yardstick_workspace_bytes": wb,
+        "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
+
+
+if __name__ == "__main__":
+    main()

@@ -270,7 +270,7 @@ static void check_devbuf() {
 }
 
 int main() {
-  CHECK(smaml_abi_version() == 7);
+  CHECK(smaml_abi_version() == 8);
   check_waves();
   check_wgrad_plans();
   check_barrier_grid();
@@ -389,6 +389,23 @@ int main() {
   CHECK(smaml_set_option(nullptr, "barrier_timeout_us", 1000) == SMAML_EINVAL);
   CHECK(smaml_meta_step(nullptr, nullptr, nullptr, 2, 1, 1, nullptr, 0.01f, 1.f, 0.5f, nullptr, nullptr, nullptr,
                         nullptr) == SMAML_EINVAL);
+  // smaml_forecast's argument checks (nothing launches): no output asked for, no windows, no context
+  {
+    const int32_t win[2] = {0, 1};
+    float* some_pred = reinterpret_cast<float*>(0x1000);   // never dereferenced: every call fails before
+    double* some_skill = reinterpret_cast<double*>(0x2000);
+    const float* some_theta = reinterpret_cast<const float*>(0x3000);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, win, 2, 2, nullptr, nullptr, nullptr) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "both NULL") != nullptr);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, win, 0, 2, nullptr, some_pred, nullptr) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "nwin") != nullptr);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, win, -3, 2, nullptr, nullptr, some_skill) == SMAML_EINVAL);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, win, 2, 0, nullptr, some_pred, nullptr) == SMAML_EINVAL);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, nullptr, 2, 2, nullptr, some_pred, nullptr) == SMAML_EINVAL);
+    CHECK(smaml_forecast(nullptr, nullptr, some_theta, 0, win, 2, 2, nullptr, some_pred, some_skill) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "ctx is NULL") != nullptr);
+    CHECK(smaml_forecast_bytes(nullptr) == 0);
+  }
   CHECK(smaml_reserve(nullptr, 1, 1) == SMAML_EINVAL);
   CHECK(smaml_set_graph(nullptr, ei.data(), E) == SMAML_EINVAL);
   CHECK(smaml_variant_counts(nullptr, nullptr, 0, nullptr, 0) == SMAML_EINVAL);

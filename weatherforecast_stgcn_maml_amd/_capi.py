@@ -24,15 +24,15 @@ EXPORTS = (
     "smaml_clip_sgd", "smaml_inner_loop", "smaml_alloc", "smaml_free", "smaml_comm_unique_id",
     "smaml_comm_init", "smaml_comm_allreduce", "smaml_comm_destroy", "smaml_variant_counts", "smaml_set_option",
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
-    "smaml_adapt_prepare", "smaml_adapt_phases",
+    "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
 )
-ABI_VERSION = 7
+ABI_VERSION = 8
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
 
 # kernels.h enum Variant: launch counters per kernel tile configuration (smaml_variant_counts)
 VARIANTS = ("fwd", "fwd_drop", "fwd_split", "fwd_img", "fwd_dual", "fwd_dual_kept", "fwd_dual_img", "bwd_big", "bwd_small", "bwd_split",
             "bwd_dual_big", "bwd_dual_big_kept", "bwd_dual_small", "bwd_dual_small_kept", "wgrad", "wgrad_wide", "wgrad_pair",
-            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact")
+            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact", "fwd_infer")
 
 # api.cpp enum Cat: one kernel per category (the bench's roofline kernel is one symbol)
 TIMING_CATEGORIES = ("gcn_layer", "lstm_fwd_step", "lstm_fwd_dual", "head_loss", "head_dh", "lstm_bwd_step",
@@ -117,6 +117,8 @@ _SIGS = {
     "smaml_relu_mask": ([P, P, P, P, I64], I32),
     "smaml_adapt_prepare": ([P, P, I32], I32),
     "smaml_adapt_phases": ([P, ctypes.POINTER(ctypes.c_double), I32, PI32, PI64], I32),
+    "smaml_forecast": ([P, P, P, I32, PI32, I32, I32, PF32, P, P], I32),
+    "smaml_forecast_bytes": ([P], I64),
 }
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
@@ -314,6 +316,22 @@ class Context:
         out = {k: ms[i] for i, k in enumerate(ADAPT_PHASES[:n.value])}
         out["windows_filled_per_step"] = filled.value
         return out
+
+    def forecast(self, stream, theta, windows, batch, task=0, scale=None, pred=None, skill=None):
+        """Rolling forecast of ``windows`` (starts into task ``task``'s stream) in passes of ``batch``:
+        ``pred`` [nwin, N*Hf, C] float32 and / or ``skill`` [3, Hf, C] float64 device tensors
+        (smaml_forecast; ``scale`` = per-variable factors of the skill sums, host, [C])."""
+        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+        if sc is not None and sc.size != self.dims.output_channels:
+            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        check(self._L.smaml_forecast(self._h, stream, ptr(theta), int(task), w.ctypes.data_as(PI32), w.size, int(batch),
+                                     sc.ctypes.data_as(PF32) if sc is not None else None,
+                                     ptr(pred) if pred is not None else None,
+                                     ptr(skill) if skill is not None else None))
+
+    def forecast_bytes(self):
+        return int(self._L.smaml_forecast_bytes(self._h))
 
     def backward(self, stream, theta, dpred, grad):
         check(self._L.smaml_backward(self._h, stream, ptr(theta), ptr(dpred), ptr(grad)))

@@ -314,6 +314,17 @@ struct smaml_ctx {
   // activations of the last smaml_forward / smaml_lstm_forward (single task, act_B samples);
   // -1 once anything else has used the workspace (the backward consumes them: dG in place)
   int act_B = -1;
+  // smaml_forecast's own buffers, sized from its pass size (grow only, never part of the arena, so a
+  // forecast leaves the workspace and everything saved in it alone): the h / c rings of the inference
+  // forward, the pass's GCN features and GCN ping-pong scratch, layer 0's projection per distinct stream
+  // row, the pass's predictions when the caller wants only the sums, the skill partials and the scale
+  HipBuf fc_ring;           // float [2][L][2][M][H]: the h ring, then the c ring
+  HipBuf fc_F;              // [T][M][Hc], or the distinct rows only (consecutive passes)
+  HipBuf fc_gcnA, fc_gcnB;  // all or none
+  HipBuf fc_xg;             // [(2B + T - 2) N][4H]
+  HipBuf fc_pred;           // [M][HfC]
+  HipBuf fc_part;           // [skill_blocks][HfC][3]
+  HipBuf fc_scale;          // [C]
   // side streams of the row-chunked BPTT (knob bptt_streams) and their fork / join events
   hipStream_t cs[4] = {};
   hipEvent_t fork_ev = nullptr, join_ev[4] = {};
@@ -727,11 +738,14 @@ bool f_compact_ok(smaml_ctx* c, bool consec) {
 // consecutive stream rows (the caller checked the window table): the rows t >= 1 are then computed
 // once per distinct stream row -- by the fused kernel (k_gcn_mlp dedup), or, on the per-layer path,
 // as one (B + T - 1) N-row pseudo-sample per task without neighbours, expanded into F afterwards.
-int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const float* const* first_tab = nullptr) {
+// fcompact >= 0: the caller decided the layout of F itself (smaml_forecast, whose readers are not the
+// training step's: forecast_compact_ok).
+int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const float* const* first_tab = nullptr,
+            int fcompact = -1) {
   const bool consec = first_tab != nullptr;
   const Dims& d = c->d;
   Work& w = c->w;
-  w.fcompact = f_compact_ok(c, consec) ? 1 : 0;
+  w.fcompact = fcompact >= 0 ? fcompact : f_compact_ok(c, consec) ? 1 : 0;
   if (w.fcompact) count_variant(w, V_F_COMPACT);
   const int rps = d.T * d.N;
   const int zb = w.Z * w.B;
@@ -1182,6 +1196,90 @@ int run_backward_dual(smaml_ctx* c, hipStream_t s, const float* theta, const flo
   return SMAML_OK;
 }
 
+// ---- smaml_forecast: inference passes on buffers of their own ---------------------------------------
+// Whether a forecast pass of consecutive windows stores its GCN features compact (the distinct stream
+// rows only, XgDedup order). The forecast's only reader of F is layer 0's gate step -- every diagonal on
+// the big tiles (k_lstm_fwd_infer has no other form) and nothing differentiates -- so unlike f_compact_ok
+// neither the weight-gradient path nor the tile choice enters: it takes the GCN and the projection once
+// per distinct row (the options of the training step) and the table they go through.
+bool forecast_compact_ok(const smaml_ctx* c, bool consec, int B, bool have_xg) {
+  const Knobs& kn = c->kn;
+  return consec && B > 1 && kn.f_compact && kn.gcn_dedup && kn.xg_dedup && have_xg;
+}
+
+// One pass of B windows of one stream (xt: their device pointer table; consec: w[b] = w[0] + b): GCN, layer
+// 0's projection per distinct stream row (consecutive passes), the inference wavefront, the head into
+// pred_out [B][N*Hf][C] and, with skill, the pass's sums added onto it. Runs in c->w (the caller saves
+// and restores the training state's) on the forecast's buffers only.
+int forecast_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
+                  float* pred_out, const float* scale_dev, double* skill, bool first) {
+  const Dims& d = c->d;
+  const Knobs& kn = c->kn;
+  const int M = B * d.N;
+  const bool dedup_gcn = consec && kn.gcn_dedup && B > 1;
+  const bool fused = gcn_mlp_supported(d) && kn.gcn_fused;
+  const bool want_xg = consec && kn.xg_dedup && B > 1;
+  const int64_t xrows = xg_dedup_rows(B, d.T, d.N);
+  const bool have_xg = want_xg && c->fc_xg.grow(xrows * 4 * d.H * 4) == hipSuccess;
+  const bool compact = forecast_compact_ok(c, consec, B, have_xg);
+  // GCN scratch rows: the t = 0 blocks on the fused path; else every row, or (per-layer dedup) each task's
+  // B + T - 1 stream rows
+  const int64_t grows = fused       ? (int64_t)M
+                        : dedup_gcn ? std::max<int64_t>((int64_t)(B + d.T - 1) * d.N, M)
+                                    : (int64_t)d.T * M;
+  const int64_t ring = infer_ring_floats(d, 1, M);
+  if (c->fc_ring.grow(2 * ring * 4) != hipSuccess ||
+      c->fc_F.grow((compact ? xrows : (int64_t)d.T * M) * d.Hc * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, grows * d.Hc * 4}, {&c->fc_gcnB, grows * d.Hc * 4}}) != hipSuccess ||
+      (!pred_out && c->fc_pred.grow((int64_t)M * d.HfC * 4) != hipSuccess) ||
+      (skill && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 3 * 4) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the forecast buffers failed (batch " + std::to_string(B) + ")");
+  Work w{};
+  w.Z = 1;
+  w.B = B;
+  w.M = M;
+  w.F = c->fc_F.as<float>();
+  w.gcnA = c->fc_gcnA.as<float>();
+  w.gcnB = c->fc_gcnB.as<float>();
+  w.vcount = c->vcount;
+  w.kn = kn;
+  c->w = w;
+  TRY(run_gcn(c, s, xt, consec ? xt : nullptr, compact ? 1 : 0));
+  TRY(prep_gate_images(c, s, theta, 0));
+  Work& cw = c->w;
+  if (have_xg) {
+    XgDedup xd{};
+    xd.zstride = xrows * 4 * d.H;
+    xd.N = d.N;
+    cw.xgd = xd;  // (zstride read by the launcher)
+    float* dst = c->fc_xg.as<float>();
+    const bool img = cw.gimg.th && cw.gimg_src == theta;
+    TIMED(c, s, C_XG, 2.0 * xrows * 4 * d.H * c->po.lay[0].cin,
+          launch_xg_dedup(s, d, cw, theta, 0, c->po, img ? cw.gimg.th : nullptr, cw.gimg.tstride, cw.gimg.off[0][0],
+                          dst));
+    xd.xg = dst;
+    xd.src = theta;
+    cw.xgd = xd;
+  }
+  float* ringH = c->fc_ring.as<float>();
+  float* ringC = ringH + ring;
+  for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+    FwdWave wv{};
+    double fl = fwd_wave(d, cw, c->po, diag, 0, false, wv);
+    if (have_xg)  // (the projection's flops are counted in C_XG)
+      for (int q = 0; q < wv.n; ++q)
+        if (wv.l[q] == 0) fl -= 2.0 * M * 4 * d.H * wv.lo[q].cin;
+    TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer(s, d, cw, diag, theta, 0, c->po, ringH, ringC));
+  }
+  float* pred = pred_out ? pred_out : c->fc_pred.as<float>();
+  TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
+        launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
+  if (skill)
+    TIMED(c, s, C_MISC, 0, launch_skill_sums(s, d, B, pred, xt, scale_dev, c->fc_part.as<float>(), skill, first));
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
 bool graph_set(const smaml_ctx* c) { return c->ell_c.ptr && c->ell_v.ptr; }
 
 int require_ready(smaml_ctx* c) {
@@ -1239,7 +1337,7 @@ extern "C" {
 
 const char* smaml_last_error(void) { return g_err.c_str(); }
 
-int32_t smaml_abi_version(void) { return 7; }
+int32_t smaml_abi_version(void) { return 8; }
 
 const char* smaml_build_info(void) { return smaml::products_info(); }
 
@@ -1559,6 +1657,71 @@ int smaml_set_tasks(smaml_ctx* c, int32_t ntasks, const float* const* features_h
     if (c->t_total[j] < c->d.T + c->d.Hf + 1) return fail(SMAML_EINVAL, "feature stream shorter than one sample");
   }
   return SMAML_OK;
+}
+
+int smaml_forecast(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
+                   int32_t nwin, int32_t batch, const float* scale_host, float* pred, double* skill) {
+  // (the checks that need no context first: they run without a device too)
+  if (!pred && !skill)
+    return fail(SMAML_EINVAL, "smaml_forecast: pred and skill are both NULL (nothing to compute)");
+  if (nwin <= 0 || batch <= 0 || !windows_host)
+    return fail(SMAML_EINVAL, "smaml_forecast: nwin and batch must be positive");
+  TRY(require_ready(c));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !aligned16(theta))
+    return fail(SMAML_EINVAL, "smaml_forecast: theta must be a 16-byte aligned device pointer");
+  if (task < 0 || task >= (int)c->feats.size()) return fail(SMAML_EINVAL, "smaml_forecast: task out of range");
+  const Dims& d = c->d;
+  const int B0 = std::min(batch, nwin);
+  if ((int64_t)d.T * B0 * d.N * 4 * d.H >= (1ll << 31))
+    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^31");
+  // a window needs its T input rows; scoring also the targets stream[w+T+1 .. w+T+Hf]
+  const int tt = c->t_total[task];
+  std::vector<const float*> ptrs(nwin);
+  for (int i = 0; i < nwin; ++i) {
+    const int wv = windows_host[i];
+    if (wv < 0 || wv + d.T > tt || (skill && wv + d.T + d.Hf >= tt))
+      return fail(SMAML_EINVAL, "smaml_forecast: window " + std::to_string(i) + " (start " + std::to_string(wv) +
+                                    (skill && wv >= 0 && wv + d.T <= tt ? ") has no targets in" : ") does not fit") +
+                                    " the stream of " + std::to_string(tt) + " steps");
+    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
+  }
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  hipStream_t s = (hipStream_t)stream;
+  // The training state stays as it is: the forecast never touches the arena, and the workspace view
+  // (with the activations a pending smaml_backward / smaml_lstm_backward will consume) is put back.
+  const Work saved = c->w;
+  const int act = c->act_B;
+  auto run = [&]() -> int {
+    const float* scale_dev = nullptr;
+    if (skill && scale_host) {
+      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
+      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
+      scale_dev = c->fc_scale.as<float>();
+    }
+    TRY(upload_xtab(c, s, ptrs.data(), nwin));
+    for (int64_t done = 0; done < nwin; done += batch) {
+      const int B = (int)std::min<int64_t>(batch, nwin - done);
+      bool consec = B > 1;
+      for (int b = 1; b < B && consec; ++b) consec = windows_host[done + b] == windows_host[done] + b;
+      const float* const* xt = nullptr;
+      TRY(xtab_at(c, done, &xt));
+      TRY(forecast_pass(c, s, theta, xt, B, consec, pred ? pred + done * d.N * d.HfC : nullptr, scale_dev, skill,
+                        done == 0));
+    }
+    return SMAML_OK;
+  };
+  const int rc = run();
+  c->w = saved;
+  c->act_B = act;
+  return rc;
+}
+
+int64_t smaml_forecast_bytes(const smaml_ctx* c) {
+  if (!c) return 0;
+  return c->fc_ring.cap + c->fc_F.cap + c->fc_gcnA.cap + c->fc_gcnB.cap + c->fc_xg.cap + c->fc_pred.cap +
+         c->fc_part.cap + c->fc_scale.cap;
 }
 
 int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,

@@ -101,6 +101,7 @@ enum Variant {
   V_XG_DEDUP,        // k_xg_dedup: layer 0's input projection once per distinct stream row (big-tile forward)
   V_WGRAD_DEDUP,     // layer 0's input-weight gradient over distinct stream rows (k_dg_rowsum + gathered k_wgrad)
   V_F_COMPACT,       // GCN features stored once per distinct stream row (Work::fcompact)
+  V_FWD_INFER,       // k_lstm_fwd_infer (smaml_forecast: only h and c kept, in a two-slot ring)
   NVAR
 };
 
@@ -440,6 +441,25 @@ void launch_xg_dedup(hipStream_t s, const Dims& d, const Work& w, const float* p
 // chunk / nch: row chunks as in launch_lstm_bwd_wave (nch > 1: every diagonal on the big tiles)
 void launch_lstm_fwd_wave(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
                           int64_t tstride, const ParamOff& po, double* flops, int chunk = 0, int nch = 1);
+// ---- inference forward (smaml_forecast; kernels.hip) ----
+// Diagonal `diag` on the big tiles whatever the size, h and c of the two most recent steps per layer in
+// the rings ringH / ringC [L][2][Z][M][H] (step t in slot t & 1; see k_lstm_fwd_infer)
+void launch_lstm_fwd_infer(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
+                           int64_t tstride, const ParamOff& po, float* ringH, float* ringC);
+inline int64_t infer_ring_floats(const Dims& d, int Z, int M) { return (int64_t)d.L * 2 * Z * M * d.H; }
+// the top layer's h_T [Z][M][H] after the last diagonal
+inline const float* infer_ring_hT(const Dims& d, const float* ringH, int Z, int M) {
+  return ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * Z * M * d.H;
+}
+// launch_head_loss's prediction alone from given h_T rows (hz floats between tasks) into pred [Z][M][HfC]
+void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
+                      int64_t tstride, const ParamOff& po, float* pred);
+// Skill sums of one pass of B windows (xtab [B] window pointers, pred [B][N*Hf][C], scale [C] or null):
+// f32 partials per block into part [skill_blocks][HfC][3], then added in double onto skill [3][Hf][C]
+// (first: overwritten). Fixed order, no atomics.
+int skill_blocks(const Dims& d, int B);
+void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, const float* const* xtab,
+                       const float* scale, float* part, double* skill, bool first);
 void launch_head_loss(hipStream_t s, const Dims& d, const Work& w, const float* theta, int64_t tstride,
                       const ParamOff& po, const float* const* xtab, float dscale, bool want_loss);
 void launch_head_loss_y(hipStream_t s, const Dims& d, const Work& w, const float* hT, const float* theta,

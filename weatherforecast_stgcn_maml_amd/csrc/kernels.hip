@@ -289,6 +289,25 @@ __device__ __forceinline__ void fwd_cell(const Acc<CfgGate>& acc, const float* _
   }
 }
 
+// The cell of one epilogue item (one row, 4 consecutive units) from its pre-activations pre[g] (bias and any
+// XG entry already added) and c_{t-1}: the gates, c_t and h_t. The training and the inference forward
+// (fwd_cell_t, infer_cell_t) both form them here, so they differ in their stores only.
+__device__ __forceinline__ void cell_item(const float4 (&pre)[4], const float4& cp, float4& gi, float4& gf, float4& gg,
+                                          float4& go, float4& c, float4& hh) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float i_ = sigmoidf_(f4get(pre[0], e)), f_ = sigmoidf_(f4get(pre[1], e));
+    const float g_ = tanhf_(f4get(pre[2], e)), o_ = sigmoidf_(f4get(pre[3], e));
+    const float c_ = lstm_cell_c(i_, f_, g_, f4get(cp, e));
+    f4set(gi, e, i_);
+    f4set(gf, e, f_);
+    f4set(gg, e, g_);
+    f4set(go, e, o_);
+    f4set(c, e, c_);
+    f4set(hh, e, o_ * tanhf_(c_));
+  }
+}
+
 // fwd_cell through the transposed epilogue (loaders.h gate_epilogue_t): per item (row, 4 units)
 // one 16-B c_{t-1} load and six 16-B stores (i, f, g, o, c, h). XG: the pre-activations also get the
 // row's XgDedup entries (layer 0's input projection, xg = the step's block of window rows): four more
@@ -330,18 +349,7 @@ __device__ __forceinline__ void fwd_cell_t(const Acc<CG>& acc, const float* __re
           }
         }
         float4 gi, gf, gg, go, c, hh;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float i_ = sigmoidf_(f4get(pre[0], e)), f_ = sigmoidf_(f4get(pre[1], e));
-          const float g_ = tanhf_(f4get(pre[2], e)), o_ = sigmoidf_(f4get(pre[3], e));
-          const float c_ = lstm_cell_c(i_, f_, g_, f4get(cp, e));
-          f4set(gi, e, i_);
-          f4set(gf, e, f_);
-          f4set(gg, e, g_);
-          f4set(go, e, o_);
-          f4set(c, e, c_);
-          f4set(hh, e, o_ * tanhf_(c_));
-        }
+        cell_item(pre, cp, gi, gf, gg, go, c, hh);
         const uint32_t og = 4u * (row * (4 * H) + jq), oh = 4u * (row * H + jq);
         sto(Gz, og, gi);
         sto(Gz, og + 4u * H, gf);
@@ -475,6 +483,105 @@ __global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_step(
   __shared__ float smem[CfgGate::SMEM_FLOATS];
   lstm_fwd_step<H, false, IMG>(F, HsAll, CsAll, GsAll, lsz, theta, tstride, wv, T, M, dr, smem, &gi, xd.xg, xd.zstride,
                                xd.N);
+}
+
+// ---- inference forward (smaml_forecast): the same gate step without the BPTT's activations ----------
+// Cell epilogue of the inference step: fwd_cell_t's arithmetic (cell_item) on the same items, but only
+// c_t and h_t are stored, into the ring slots Cn / Hn ([M][H] each); c_{t-1} comes from the slot Cp.
+template <int H, class CG>
+__device__ __forceinline__ void infer_cell_t(const Acc<CG>& acc, const float* __restrict__ th, const LayerOff& lo,
+                                             const float* __restrict__ Cp, float* __restrict__ Cn,
+                                             float* __restrict__ Hn, int m0, int ug, bool past, int M, float* smem,
+                                             const float* xg) {
+  const int j = ug * 32 + (int)(threadIdx.x & 31);
+  float bsum[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) bsum[g] = j < H ? th[lo.bih + g * H + j] + th[lo.bhh + g * H + j] : 0.f;
+  const bool full = m0 + CG::BM <= M;
+  gate_epilogue_t<CG>(
+      acc, bsum, smem,
+      [&](int ml, int u) {
+        int m = m0 + ml;
+        if (!full) m = min(m, M - 1);  // clamped rows read a valid address (not stored)
+        const int jq = min(ug * 32 + u, H - 4);
+        return ldo(Cp, 4u * ((uint32_t)m * H + (uint32_t)jq));  // c_{t-1} (t = 0: selected out)
+      },
+      [&](int ml, int u, const float4 (&pre0)[4], const float4& cpv) {
+        if ((!full && m0 + ml >= M) || ug * 32 + u >= H) return;
+        const uint32_t row = (uint32_t)(m0 + ml), jq = (uint32_t)(ug * 32 + u);
+        const float4 cp = sel4(past, cpv);
+        float4 pre[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          pre[g] = pre0[g];
+          if (xg) {
+            const float4 x = ldo(xg, 4u * (row * (4 * H) + (uint32_t)(g * H) + jq));
+            pre[g] = make_float4(pre[g].x + x.x, pre[g].y + x.y, pre[g].z + x.z, pre[g].w + x.w);
+          }
+        }
+        float4 gi, gf, gg, go, c, hh;
+        cell_item(pre, cp, gi, gf, gg, go, c, hh);
+        const uint32_t oh = 4u * (row * H + jq);
+        sto(Cn, oh, c);
+        sto(Hn, oh, hh);
+      });
+}
+
+// One anti-diagonal of the LSTM forward for inference: k_lstm_fwd_step's tile (CfgGate), mainloop, operand
+// loaders, weight images and XG-table handling, with only h and c kept, in a two-slot ring per layer:
+// ringH / ringC are [L][2][Z][M][H], step t of layer l lives in slot t & 1.
+// Why two slots suffice: on diagonal d problem (l, t), l + t = d, reads h(l-1, t) (slot t & 1 of layer l-1)
+// and h(l, t-1), c(l, t-1) (slot (t-1) & 1 of layer l), all written on diagonal d-1, and writes slot t & 1
+// of layer l, which held step t-2. Step (l, t-2)'s readers were (l, t-1) and (l+1, t-2), both on diagonal
+// d-1: done. The only other problem of diagonal d that touches layer l's ring is (l+1, t-1), which reads
+// h(l, t-1) in slot (t-1) & 1 -- the other slot -- and layer l-1's slot t & 1 is written by (l-1, t+1) on
+// diagonal d too, but into slot (t+1) & 1 = the other one. So no launch writes a slot that it, or a problem
+// sharing its launch, reads. Layer L-1's step T-1 leaves h_T in slot (T-1) & 1 of the top layer, where
+// the head reads it. No dropout (eval mode); big tiles at every size, masked at the edges.
+template <int H, bool IMG>
+__global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_infer(
+    const float* __restrict__ F, float* __restrict__ ringH, float* __restrict__ ringC,
+    const float* __restrict__ theta, int64_t tstride, FwdWave wv, int T, int M, GateImgs gi, XgDedup xd) {
+  __shared__ float smem[CfgGate::SMEM_FLOATS];
+  int l, t, b0;
+  LayerOff lo;
+  const Blk bk = xcd_block();
+  wave_problem(wv, bk.x, l, t, lo, b0);
+  const int z = bk.z, Z = (int)gridDim.z;
+  const int64_t slot = (int64_t)M * H;  // floats of one task's rows in one slot
+  auto at = [&](float* ring, int ll, int tt) { return ring + ((int64_t)(2 * ll + (tt & 1)) * Z + z) * slot; };
+  const float* th = theta + (int64_t)z * tstride;
+  const int cin = lo.cin;
+  const float* Hp = t > 0 ? at(ringH, l, t - 1) : nullptr;
+  int tm, ug;
+  constexpr int UPB = CfgGate::WAVES_N;
+  if (!gate_tile(bk.x - b0, (M + CfgGate::BM - 1) / CfgGate::BM, (H + 32 * UPB - 1) / (32 * UPB), tm, ug)) return;
+  const int m0 = tm * CfgGate::BM, n0 = ug * CfgGate::BN;
+  Acc<CfgGate> acc;
+  acc.zero();
+  // XG: layer 0's input projection comes from the XgDedup table (added in the epilogue, as in lstm_fwd_step),
+  // the K loop starts past the input segment and F (which may be compact) is not read
+  const float* xgt = xd.xg && l == 0 ? xd.xg + (int64_t)z * xd.zstride + xg_dedup_row0(t, M, xd.N) * (4 * H) : nullptr;
+  const int kbeg = xgt ? cin : 0;
+  const float* X = l > 0 ? at(ringH, l - 1, t) : xgt ? F : F + ((int64_t)z * T + t) * M * cin;
+  const SegKCt<2> la{{X, Hp}, {cin, H}, M};
+  if constexpr (IMG) {
+    const char* ib = gi.th + (int64_t)z * gi.tstride;
+    int64_t o0 = 0, o1 = 0;
+#pragma unroll
+    for (int q = 0; q < MAX_LAYERS; ++q)
+      if (q == l) {
+        o0 = gi.off[q][0];
+        o1 = gi.off[q][1];
+      }
+    const SegGateImg<2> lbi{{ib + o0, ib + o1}, {cin, H}};
+    gemm_mainloop<CfgGate>(la, lbi, m0, n0, kbeg, cin + (t > 0 ? H : 0), acc, smem);
+  } else {
+    const SegGateBt<2> lbt{{th + lo.wih, th + lo.whh}, {cin, H}, H};
+    gemm_mainloop<CfgGate>(la, lbt, m0, n0, kbeg, cin + (t > 0 ? H : 0), acc, smem);
+  }
+  infer_cell_t<H, CfgGate>(acc, th, lo, at(ringC, l, t - 1), at(ringC, l, t), at(ringH, l, t), m0, ug, t > 0, M, smem,
+                           xgt);
 }
 
 // Layer 0's input projection of a step whose every task reads B consecutive windows, once per distinct
@@ -854,6 +961,29 @@ void launch_lstm_fwd_wave(hipStream_t s, const Dims& d, const Work& w, int diag,
   }
 }
 
+// Diagonal `diag` of the inference forward (k_lstm_fwd_infer): always the big tiles -- no split-K or kw
+// form, a small grid is the caller's to avoid through its pass size. Reads w.F / w.gimg / w.xgd like
+// launch_lstm_fwd_wave; the activations go to the ring instead of w.Hs / w.Cs / w.Gs.
+void launch_lstm_fwd_infer(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
+                           int64_t tstride, const ParamOff& po, float* ringH, float* ringC) {
+  const int ntm = (w.M + CfgGate::BM - 1) / CfgGate::BM;
+  const int ngrp = (d.H + 32 * CfgGate::WAVES_N - 1) / (32 * CfgGate::WAVES_N);
+  FwdWave wv{};
+  fwd_wave(d, w, po, diag, gate_blocks(ntm, ngrp), false, wv);
+  if (wv.n == 0) return;
+  dim3 grid(wv.off[wv.n], 1, w.Z);
+  count_variant(w, V_FWD_INFER);
+  XgDedup xd = w.xgd;
+  if (xd.src != theta) xd.xg = nullptr;  // (a table of other weights is never read)
+  if (w.gimg.th && w.gimg_src == theta) {
+    SMAML_DISPATCH_H(d.H, (k_lstm_fwd_infer<HT, true><<<grid, CfgGate::NTH, 0, s>>>(w.F, ringH, ringC, theta, tstride, wv,
+                                                                                    d.T, w.M, w.gimg, xd)));
+  } else {
+    SMAML_DISPATCH_H(d.H, (k_lstm_fwd_infer<HT, false><<<grid, CfgGate::NTH, 0, s>>>(w.F, ringH, ringC, theta, tstride,
+                                                                                     wv, d.T, w.M, w.gimg, xd)));
+  }
+}
+
 // ---- pre-split gate-GEMM weight images --------------------------------------------------
 int64_t gate_img_bytes(const Dims& d, GateImgs* gi) {
   const int nug = (d.H + 31) / 32;
@@ -1174,6 +1304,80 @@ __global__ void k_loss_final(const float* __restrict__ lpart, int lblocks, float
 
 void launch_loss_final(hipStream_t s, const Work& w, float inv_count, float* out) {
   k_loss_final<<<w.Z, NT, 0, s>>>(w.lpart, w.lblocks, inv_count, out);
+}
+
+// The head of the inference forward: launch_head_loss's prediction (same kernel per size, no targets)
+// from the rows hT [Z][M][H] (hz floats between tasks) into pred [Z][M][HfC].
+void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
+                      int64_t tstride, const ParamOff& po, float* pred) {
+  if (head_small(d, w.M)) {
+    k_head_loss_small<<<dim3(w.M, 1, w.Z), head_small_threads(d), 0, s>>>(
+        hT, hz, theta, tstride, po.wo, po.bo, nullptr, pred, nullptr, nullptr, 0, w.M, d.H, d.HfC, d.N, d.Hf, d.C,
+        d.T + 1, d.Cin0, w.B, 0.f);
+    return;
+  }
+  dim3 grid((w.M + CfgNT::BM - 1) / CfgNT::BM, 1, w.Z);
+  k_head_loss<<<grid, NT, 0, s>>>(hT, hz, theta, tstride, po.wo, po.bo, nullptr, pred, nullptr, nullptr, 0, w.M, d.H,
+                                  d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, 0.f);
+}
+
+// ---- forecast skill sums (smaml_forecast) ---------------------------------------------------------
+// Per target lead h' and variable c, over the B windows of a pass, with k_head_loss's F4 pairing (flat
+// prediction row r = n Hf + h of a window is compared with target (h' = r / N, n' = r % N), so lead h'
+// owns the rows r in [h' N, (h' + 1) N)):
+//   [0] sum (s_c (p - y))^2, [1] sum |s_c (p - y)|, [2] sum (s_c (y_last - y))^2 (persistence),
+// y = stream[w + T + 1 + h', n', c], y_last = stream[w + T - 1, n', c] (the last observed value).
+// Block (h' C + c, k) sums the (window, n') pairs [k SKILL_PAIRS, (k + 1) SKILL_PAIRS) in f32 (each thread
+// its pairs in order, then block_sum's fixed tree) into part[k][h' C + c][3]; k_skill_final adds the
+// blocks in order in double onto skill [3][Hf][C] (first pass: overwrites). No atomics: bitwise repeatable.
+constexpr int SKILL_PAIRS = 1024;
+__global__ __launch_bounds__(NT) void k_skill_part(const float* __restrict__ pred, const float* const* __restrict__ xtab,
+                                                   const float* __restrict__ scale, int B, int N, int Hf, int C, int T,
+                                                   int yld, float* __restrict__ part) {
+  __shared__ float red[NT / 64];
+  const int hc = blockIdx.x, hp = hc / C, c = hc - hp * C;
+  const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, B * N);
+  const float sc = scale ? scale[c] : 1.f;
+  float se = 0.f, ae = 0.f, pe = 0.f;
+  for (int p = p0 + (int)threadIdx.x; p < p1; p += NT) {
+    const int sm = p / N, n = p - sm * N;
+    const float* xs = xtab[sm];
+    const float y = xs[((int64_t)(T + 1 + hp) * N + n) * yld + c];
+    const float yl = xs[((int64_t)(T - 1) * N + n) * yld + c];
+    const float pv = pred[((int64_t)sm * N * Hf + (int64_t)hp * N + n) * C + c];
+    const float e = sc * (pv - y), q = sc * (yl - y);
+    se = fmaf(e, e, se);
+    ae += fabsf(e);
+    pe = fmaf(q, q, pe);
+  }
+  float* o = part + ((int64_t)blockIdx.y * gridDim.x + hc) * 3;
+  const float s0 = block_sum(se, red);
+  const float s1 = block_sum(ae, red);
+  const float s2 = block_sum(pe, red);
+  if (threadIdx.x == 0) {
+    o[0] = s0;
+    o[1] = s1;
+    o[2] = s2;
+  }
+}
+
+__global__ void k_skill_final(const float* __restrict__ part, int nblk, int HfC, double* __restrict__ skill,
+                              int first) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 3 * HfC) return;
+  const int k = i / HfC, hc = i - k * HfC;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += (double)part[((int64_t)b * HfC + hc) * 3 + k];
+  skill[i] = first ? s : skill[i] + s;
+}
+
+int skill_blocks(const Dims& d, int B) { return (B * d.N + SKILL_PAIRS - 1) / SKILL_PAIRS; }
+
+void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, const float* const* xtab,
+                       const float* scale, float* part, double* skill, bool first) {
+  const int nblk = skill_blocks(d, B);
+  k_skill_part<<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part);
+  k_skill_final<<<(3 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, skill, first ? 1 : 0);
 }
 
 // ====================================================================================

@@ -1,0 +1,143 @@
+"""Rolling forecast of an adapted model over a region's feature stream, with per-lead-time,
+per-variable skill in physical units (``smaml_forecast``).
+
+What the reference stops short of: ``validate_hybrid_v5.validateAdapted`` (validate_hybrid_v5.py:189-237)
+scores ``min(3, n)`` windows and ``adaptModel``'s validation loop (adapt_hybrid_v5.py:216-231) gives one
+scalar MSE. ``forecast`` runs every window of the stream -- including, without scoring, the windows whose
+targets lie past its end -- through the inference-only forward of the library and returns the predictions
+and RMSE / MAE per target lead and variable, beside the persistence baseline (the last observed value
+held for every lead) and the skill ``1 - SSE / SSE_persistence``.
+
+The pairing of predictions and targets is the one the model was trained with and the reference's
+evaluation uses (validate_hybrid_v5.py:224-237): the flat prediction rows ``[N*Hf]`` are
+viewed as ``[Hf, N]``, so flat row ``r`` meets target ``(h' = r // N, n' = r % N)``. Kept, not fixed.
+
+``skill_reference`` states the sums in numpy (float64) from given predictions; the GPU tests hold the
+library to it.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+
+SUMS = ("sse", "sae", "persistence_sse")  # order of smaml_forecast's skill sums
+
+
+def default_windows(t_total: int, window: int, horizon: int, score: bool) -> np.ndarray:
+    """Window starts of a ``t_total``-step stream: with ``score`` every window whose targets
+    ``stream[w+T+1 .. w+T+Hf]`` exist (``len(WeatherGraphDataset)``, dataset.py:25), else every window
+    whose inputs exist (``w + T <= t_total``; the last ``Hf + 1`` forecast past the end of the stream)."""
+    n = max(0, t_total - window - horizon) if score else max(0, t_total - window + 1)
+    return np.arange(n, dtype=np.int32)
+
+
+def skill_reference(pred_norm, features, windows: Sequence[int], dims, scale=None) -> np.ndarray:
+    """The three skill sums ``[3, Hf, C]`` (float64; order ``SUMS``) of normalised predictions
+    ``pred_norm [nwin, N*Hf, C]`` for the windows ``windows`` of ``features [t_total, N, >= C]``:
+    ``sum (s_c (p - y))^2``, ``sum |s_c (p - y)|`` and ``sum (s_c (y_last - y))^2`` over windows and
+    nodes, with ``y = features[w+T+1+h', n', c]``, ``y_last = features[w+T-1, n', c]`` and the F4 pairing
+    (module docstring). Pure numpy; needs no GPU."""
+    T, Hf, N, C = dims.window_size, dims.forecast_horizon, dims.num_nodes, dims.output_channels
+    p_all = np.asarray(pred_norm, np.float64).reshape(len(windows), Hf, N, C)  # flat rows seen as [Hf, N]
+    f = np.asarray(features)
+    s = np.ones(C) if scale is None else np.asarray(scale, np.float64).reshape(C)
+    out = np.zeros((3, Hf, C))
+    for p, w in zip(p_all, windows):
+        w = int(w)
+        if w < 0 or w + T + Hf >= f.shape[0]:
+            raise ValueError(f"window {w} has no targets in a stream of {f.shape[0]} steps")
+        y = f[w + T + 1:w + T + 1 + Hf, :, :C].astype(np.float64)
+        y_last = f[w + T - 1, :, :C].astype(np.float64)[None]
+        e = (p - y) * s
+        q = (y_last - y) * s
+        out[0] += (e * e).sum(axis=1)
+        out[1] += np.abs(e).sum(axis=1)
+        out[2] += (q * q).sum(axis=1)
+    return out
+
+
+@dataclass
+class ForecastResult:
+    pred: Optional[np.ndarray]              # [nwin, Hf, N, C], physical units over the first len(std) variables
+    rmse: Optional[np.ndarray]              # [Hf, C]
+    mae: Optional[np.ndarray]               # [Hf, C]
+    persistence_rmse: Optional[np.ndarray]  # [Hf, C]
+    skill: Optional[np.ndarray]             # [Hf, C]: 1 - SSE / SSE_persistence, NaN where the baseline error is 0
+    n_windows: int
+    windows: np.ndarray                     # the window starts that were run
+
+
+def skill_metrics(sums: np.ndarray, count: int):
+    """(rmse, mae, persistence_rmse, skill) ``[Hf, C]`` from the sums ``[3, Hf, C]`` over ``count``
+    (window, node) pairs per entry."""
+    sums = np.asarray(sums, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        skill = np.where(sums[2] > 0, 1.0 - sums[0] / sums[2], np.nan)
+    return np.sqrt(sums[0] / count), sums[1] / count, np.sqrt(sums[2] / count), skill
+
+
+def _stats(stats, C):
+    """(mean, std) of the adaptation checkpoint's ``stats`` padded to C variables with (0, 1)."""
+    mean, std = np.zeros(C), np.ones(C)
+    if stats is not None:
+        m = np.asarray(stats["mean"] if isinstance(stats, dict) else stats[0], np.float64).reshape(-1)[:C]
+        s = np.asarray(stats["std"] if isinstance(stats, dict) else stats[1], np.float64).reshape(-1)[:C]
+        mean[:len(m)] = m
+        std[:len(s)] = s
+    return mean, std
+
+
+def forecast(model, features, edge_index, stats=None, windows=None, batch: int = 64, score: bool = True,
+             return_pred: bool = True, ctx=None) -> ForecastResult:
+    """``model``: the drop-in ``HybridSTGCN_LSTM`` (its weights, prepared as ``evaluate_regional``
+    prepares it); ``features``: the region's normalised ``[T_total, N, 24]`` stream (a tensor on the HIP
+    device or a numpy array); ``stats``: ``{"mean": [..], "std": [..]}`` of the adaptation checkpoint
+    (None: normalised units). ``windows``: window starts (default: ``default_windows``). The windows
+    run in passes of ``batch``; consecutive windows share their GCN features and input projections.
+    ``score=False`` forecasts only (windows may then reach the end of the stream); ``return_pred=False``
+    keeps the predictions on the device pass by pass and returns the metrics alone. ``ctx``: a
+    ``_capi.Context`` of the model's shape to run on (default: the model's own cached one)."""
+    import torch
+
+    from . import _capi
+    from .model import _set_graph
+
+    if not score and not return_pred:
+        raise ValueError("forecast(score=False, return_pred=False) has nothing to return")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _capi.SmamlError(-1, "forecast runs on a HIP device only")
+    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
+    f = f.to(dev, torch.float32).contiguous()
+    T = model.base_stgcn.window_size
+    Hf, C = model.forecast_horizon, model.out_channels
+    t_total, N = int(f.shape[0]), int(f.shape[1])
+    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    if ctx is None:
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+    else:
+        dims = model.dims(N)
+        _set_graph(ctx, ei)
+        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
+        ctx.set_gcn_params(gflat)
+        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
+    w = default_windows(t_total, T, Hf, score) if windows is None else np.asarray(windows, np.int32).reshape(-1)
+    if w.size == 0:
+        return ForecastResult(None, None, None, None, None, 0, w)
+    ctx.set_tasks([f])
+    mean, std = _stats(stats, C)
+    pred = torch.empty(w.size, N * Hf, C, device=dev) if return_pred else None
+    sums = torch.empty(3, Hf, C, device=dev, dtype=torch.float64) if score else None
+    with torch.no_grad():
+        ctx.forecast(_capi.stream_ptr(torch), theta, w, batch, scale=std if score else None, pred=pred, skill=sums)
+        out = None
+        if pred is not None:
+            scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
+            shift_t = torch.from_numpy(mean.astype(np.float32)).to(dev)
+            out = (pred * scale_t + shift_t).view(w.size, Hf, N, C).cpu().numpy()
+    if not score:
+        return ForecastResult(out, None, None, None, None, int(w.size), w)
+    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), int(w.size) * N)
+    return ForecastResult(out, rmse, mae, prmse, skill, int(w.size), w)
