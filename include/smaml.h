@@ -220,6 +220,26 @@ int smaml_adapt_steps(smaml_ctx* ctx, void* stream, float* theta, float* m, floa
  * first call when this was not called. No compute; the cache stays cold. */
 int smaml_adapt_prepare(smaml_ctx* ctx, void* stream, int32_t batch);
 
+/* Several regions adapted in lockstep (main.py adapts its regions one after another; they are independent
+ * problems of one shape): region r is task tasks_host[r] of smaml_set_tasks (distinct, in range), with
+ * its own theta / m / v [nregions][P], learning rates lr_dev [nsteps][nregions] (device), weight decay
+ * weight_decay_host [nregions] and windows windows_host [nsteps][nregions][batch] (starts into that
+ * region's stream, validated against its length). For every k, step k of all regions runs as one set of
+ * launches over the task axis; all regions share the Adam step step0+k+1. Region r computes what
+ * smaml_adapt_steps computes on that stream alone with that region's theta, m, v, lr and weight decay
+ * (one region: bitwise). losses [nsteps][nregions] (device). Nothing synchronises the stream; the
+ * per-step tables are uploaded once per call. Every region has a GCN feature cache of its own (batch 1,
+ * no GCN dropout); when one of them does not fit, all regions compute their GCN per step. Dropout masks
+ * are keyed by each region's id of smaml_set_task_ids (all ids 0: the single-region masks in every
+ * region). smaml_set_option("adapt_group", g) runs the regions g at a time (0 = all at once; default: see there). */
+int smaml_adapt_steps_multi(smaml_ctx* ctx, void* stream, int32_t nregions, const int32_t* tasks_host,
+                            float* theta, float* m, float* v, int32_t step0, int32_t nsteps, int32_t batch,
+                            const int32_t* windows_host, const float* lr_dev, const float* weight_decay_host,
+                            float beta1, float beta2, float eps, float max_norm, float* losses);
+/* smaml_adapt_prepare for the regions of a lockstep call: the workspace and every region's feature cache. */
+int smaml_adapt_prepare_multi(smaml_ctx* ctx, void* stream, int32_t nregions, const int32_t* tasks_host,
+                              int32_t batch);
+
 /* Host-timed phases of the last smaml_adapt_steps call, in ms: [0] workspace reserve, [1] feature-
  * cache allocation, [2] the batched feature-cache fill, [3] the step loop ([2] and [3] are enqueue
  * times unless smaml_set_option("adapt_phase_sync", 1), which ends each with a stream sync).
@@ -364,6 +384,11 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  runs of up to this many consecutive missing windows per GCN pass
  *                                  (default 32; 0 or 1 = one window per step as it is first read;
  *                                  bitwise equal);
+ *   "adapt_group":                 smaml_adapt_steps_multi runs its regions this many at a time, each group
+ *                                  as one set of launches per step (0: all at once; at most 64; -1, the
+ *                                  default: the measured plan -- 3 to 5 regions in sets of 2, where a set
+ *                                  of that size is slower per region than one region alone, every other
+ *                                  count all at once);
  *   "adapt_phase_sync":            smaml_adapt_steps synchronises its stream after the feature-cache fill
  *                                  and after the step loop so smaml_adapt_phases reports GPU time (0,
  *                                  the default; measurement only);

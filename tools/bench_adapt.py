@@ -9,6 +9,15 @@ first use and reused by later epochs), the first / later epoch and validation ti
 sample-steps on this host. Synthetic ERA5-shaped stream (seed 1000), random-init weights.
 
 Usage: python tools/bench_adapt.py [--epochs 15] [--warmup 1] [--cpu-sample-steps 4]
+
+--regions R: R regions (R streams, seeds 1000..) adapted in lockstep (smaml_adapt_steps_multi, one call per
+epoch) against the same R regions adapted one after another on the single-region path (smaml_adapt_steps,
+a fresh context per region, as main.py's loop pays it), in the same process. One JSON line: ms per lockstep
+step and region-sample-steps/s of the first epoch and of the later epochs (min / median / max over the
+later epochs: each is one repetition; --epochs 6 gives five), the set-up time (workspace + feature caches,
+smaml_adapt_prepare[_multi]), the bytes the set-up took, the ratio sequential / lockstep, and with
+--timing the per-category kernel time of one more lockstep epoch. --adapt-group g runs g regions per
+launch set (option adapt_group); --no-sequential skips the yardstick.
 """
 from __future__ import annotations
 
@@ -31,7 +40,13 @@ def main():
     p.add_argument("--max-samples", type=int, default=1200)
     p.add_argument("--cpu-sample-steps", type=int, default=4)
     p.add_argument("--region", default="Amazon")
+    p.add_argument("--regions", type=int, default=0, help="R > 0: lockstep adaptation of R regions vs sequential")
+    p.add_argument("--adapt-group", type=int, default=-1, help="option adapt_group of the lockstep run (-1: the default plan)")
+    p.add_argument("--no-sequential", action="store_true")
+    p.add_argument("--timing", action="store_true", help="one more lockstep epoch with per-category kernel timing")
     a = p.parse_args()
+    if a.regions > 0:
+        return regions_main(a)
     import torch
 
     from weatherforecast_stgcn_maml_amd import _capi, adapt, params, synth
@@ -125,6 +140,159 @@ def main():
                                "sample": f"{a.cpu_sample_steps} batch-1 sample-steps of the reference's per-node "
                                          f"nn.LSTM CPU path at N=441, {t_cpu:.3f} s each"}
         out["vs_cpu_baseline"] = out["value"] * t_cpu
+    print(json.dumps(out))
+
+
+REGION_NAMES = ("Amazon", "Thailand", "Moscow", "Delhi", "Indonesia", "NorthSiberia", "Sahara", "QueensAustralia",
+                "Afghanistan", "Alps", "Andes", "Congo", "Gobi", "Iberia", "Japan", "Kalahari", "Patagonia", "Texas")
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return {"min": xs[0], "median": xs[len(xs) // 2], "max": xs[-1], "n": len(xs)} if xs else None
+
+
+def regions_main(a):
+    import torch
+
+    from weatherforecast_stgcn_maml_amd import _capi, adapt, params, synth
+    from weatherforecast_stgcn_maml_amd.config import SEED, ModelDims
+    from weatherforecast_stgcn_maml_amd.graph import build_spatial_graph
+
+    R = a.regions
+    d = ModelDims(num_nodes=441, hidden_channels=256)
+    lats, lons = synth.region_grid(n_lat=21, n_lon=21)
+    ei, _, _ = build_spatial_graph(lats, lons, 4)
+    P = synth.init_params(SEED, d)
+    names = [k for k in P if k.startswith(("lstm.", "output_layer."))]
+    gcn = {k: v for k, v in P.items() if k not in names}
+    theta = {k: P[k] for k in names}
+    T_total = a.max_samples + d.window_size + d.forecast_horizon
+    dev = torch.device("cuda:0")
+    n_max = min(a.max_samples, synth.num_samples(T_total, d.window_size, d.forecast_horizon))
+    n_train = int(0.8 * n_max)
+    regions = [REGION_NAMES[r % len(REGION_NAMES)] for r in range(R)]
+    cfgs = [adapt.climate_optimizer_config(n, 0.0006) for n in regions]
+    streams = [torch.from_numpy(np.ascontiguousarray(synth.make_features(synth.task_seed(r), d.num_nodes, T_total))).to(dev)
+               for r in range(R)]
+    stream = _capi.stream_ptr(torch)
+    gflat = params.pack(gcn, d, which=1, device=dev)
+    th0 = params.pack(theta, d, which=0, device=dev)
+    torch.manual_seed(SEED)
+    orders = [[adapt.random_sampler_order(n_train).numpy().astype(np.int32) for _ in range(a.epochs + 1)]
+              for _ in range(R)]
+    cache_bytes = T_total * d.window_size * d.num_nodes * d.hidden_channels * 4
+
+    def context(tasks):
+        ctx = _capi.Context(d, 0)
+        ctx.set_graph(ei)
+        ctx.set_gcn_params(gflat)
+        ctx.set_tasks(tasks)
+        ctx.set_task_ids([0] * len(tasks))
+        return ctx
+
+    def used():
+        free, total = torch.cuda.mem_get_info()
+        return total - free
+
+    def lockstep(n_epochs, n_steps=n_train, timing=False):
+        """A fresh context adapting all R regions in lockstep -> (setup s, bytes, per-epoch s, mean last loss)."""
+        ctx = context(streams)
+        ctx.set_option("adapt_group", a.adapt_group)
+        torch.cuda.synchronize()
+        u0, t0 = used(), time.perf_counter()
+        ctx.adapt_prepare_multi(stream, list(range(R)), 1)
+        torch.cuda.synchronize()
+        setup, took = time.perf_counter() - t0, used() - u0
+        th = th0.unsqueeze(0).repeat(R, 1).contiguous()
+        m, v = torch.zeros_like(th), torch.zeros_like(th)
+        losses = torch.empty(n_steps, R, device=dev)
+        lr_dev = torch.tensor([c[0] for c in cfgs], dtype=torch.float32).to(dev).repeat(n_steps, 1).contiguous()
+        per, cats = [], None
+        for ep in range(n_epochs + (1 if timing else 0)):
+            w = np.stack([orders[r][ep][:n_steps] for r in range(R)], axis=1).reshape(n_steps, R, 1)
+            timed = timing and ep == n_epochs
+            if timed:
+                ctx.timing(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ctx.adapt_steps_multi(stream, list(range(R)), th, m, v, ep * n_steps, w, lr_dev, (0.9, 0.999), 1e-8,
+                                  [c[1] for c in cfgs], adapt.MAX_GRAD_NORM, losses)
+            torch.cuda.synchronize()
+            if timed:
+                cats = {k: {"us_per_step": c["ms"] * 1e3 / n_steps, "launches_per_step": c["launches"] / n_steps}
+                        for k, c in ctx.timing_collect().items() if c["launches"]}
+                ctx.timing(False)
+            else:
+                per.append(time.perf_counter() - t0)
+        loss = losses.double().mean(dim=0).cpu().numpy()
+        vc = {k: n for k, n in ctx.variant_counts().items() if n}
+        ctx.close()
+        return setup, took, per, loss, cats, vc
+
+    def sequential(n_epochs, n_steps=n_train):
+        """Each region on a fresh single-region context, one after another -> the same, summed over regions."""
+        setup, took, per, loss = 0.0, 0, [0.0] * n_epochs, []
+        for r in range(R):
+            ctx = context([streams[r]])
+            torch.cuda.synchronize()
+            u0, t0 = used(), time.perf_counter()
+            ctx.adapt_prepare(stream, 1)
+            torch.cuda.synchronize()
+            setup += time.perf_counter() - t0
+            took = max(took, used() - u0)
+            th = th0.clone()
+            m, v = torch.zeros_like(th), torch.zeros_like(th)
+            losses = torch.empty(n_steps, device=dev)
+            lr_dev = torch.full((n_steps,), cfgs[r][0], device=dev, dtype=torch.float32)
+            for ep in range(n_epochs):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ctx.adapt_steps(stream, th, m, v, ep * n_steps, orders[r][ep][:n_steps].reshape(n_steps, 1), lr_dev,
+                                (0.9, 0.999), 1e-8, cfgs[r][1], adapt.MAX_GRAD_NORM, losses)
+                torch.cuda.synchronize()
+                per[ep] += time.perf_counter() - t0
+            loss.append(float(losses.double().mean().item()))
+            ctx.close()
+        return setup, took, per, np.asarray(loss)
+
+    for _ in range(a.warmup):  # module load, first touch: a short epoch of each path
+        lockstep(1, min(16, n_train))
+        if not a.no_sequential:
+            sequential(1, min(16, n_train))
+
+    def report(setup, took, per):
+        later = [t / n_train * 1e3 for t in per[1:]]
+        return {"setup_ms": setup * 1e3, "setup_bytes": took, "first_epoch_ms": per[0] * 1e3,
+                "first_epoch_ms_per_step": per[0] / n_train * 1e3, "later_ms_per_step": spread(later),
+                "later_region_sample_steps_per_s": spread([R * 1e3 / t for t in later])}
+
+    setup, took, per, loss, cats, vc = lockstep(a.epochs, timing=a.timing)
+    out = {
+        "metric": "lockstep regional adaptation, region-sample-steps/s of the later epochs (median)",
+        "regions": R, "adapt_group": a.adapt_group, "epochs": a.epochs, "train_samples": n_train,
+        "cache_bytes_per_region": cache_bytes, "lockstep": report(setup, took, per),
+        "caches_fit": bool(took >= R * cache_bytes), "train_loss_last_epoch": loss.tolist(), "variants": vc,
+        "config": "N=441, Hc=256, LSTM 4x128, batch-1 steps, GCN features cached per (region, window)",
+    }
+    assert np.isfinite(loss).all(), loss
+    if out["lockstep"]["later_region_sample_steps_per_s"]:
+        out["value"] = out["lockstep"]["later_region_sample_steps_per_s"]["median"]
+        out["unit"] = "region-sample-steps/s"
+    if cats:
+        out["timing_us_per_lockstep_step"] = cats
+    if not a.no_sequential:
+        setup, took, sper, sloss = sequential(a.epochs)
+        out["sequential"] = report(setup, took, sper)
+        out["loss_rel_diff_vs_sequential"] = float(np.max(np.abs(loss - sloss) / np.abs(sloss)))
+        lo, sq = out["lockstep"]["later_ms_per_step"], out["sequential"]["later_ms_per_step"]
+        if lo and sq:
+            out["speedup_later"] = {"median": sq["median"] / lo["median"], "worst": sq["min"] / lo["max"],
+                                    "best": sq["max"] / lo["min"],
+                                    "beats_by_more_than_both_spreads": bool(
+                                        sq["median"] - lo["median"] > (sq["max"] - sq["min"]) + (lo["max"] - lo["min"]))}
+        out["speedup_first_epoch_with_setup"] = ((out["sequential"]["first_epoch_ms"] + out["sequential"]["setup_ms"]) /
+                                                 (out["lockstep"]["first_epoch_ms"] + out["lockstep"]["setup_ms"]))
     print(json.dumps(out))
 
 

@@ -270,7 +270,7 @@ static void check_devbuf() {
 }
 
 int main() {
-  CHECK(smaml_abi_version() == 8);
+  CHECK(smaml_abi_version() == 9);
   check_waves();
   check_wgrad_plans();
   check_barrier_grid();

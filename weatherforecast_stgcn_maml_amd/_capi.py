@@ -25,8 +25,9 @@ EXPORTS = (
     "smaml_comm_init", "smaml_comm_allreduce", "smaml_comm_destroy", "smaml_variant_counts", "smaml_set_option",
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
+    "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi",
 )
-ABI_VERSION = 8
+ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
 
 # kernels.h enum Variant: launch counters per kernel tile configuration (smaml_variant_counts)
@@ -119,6 +120,8 @@ _SIGS = {
     "smaml_adapt_phases": ([P, ctypes.POINTER(ctypes.c_double), I32, PI32, PI64], I32),
     "smaml_forecast": ([P, P, P, I32, PI32, I32, I32, PF32, P, P], I32),
     "smaml_forecast_bytes": ([P], I64),
+    "smaml_adapt_steps_multi": ([P, P, I32, PI32, P, P, P, I32, I32, I32, PI32, P, PF32, F32, F32, F32, F32, P], I32),
+    "smaml_adapt_prepare_multi": ([P, P, I32, PI32, I32], I32),
 }
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
@@ -307,6 +310,31 @@ class Context:
     def adapt_prepare(self, stream, batch=1):
         """Workspace + per-window feature cache for adapt_steps, allocated and touched now (no compute)."""
         check(self._L.smaml_adapt_prepare(self._h, stream, int(batch)))
+
+    def adapt_steps_multi(self, stream, tasks, theta, m, v, step0, windows: np.ndarray, lr_dev, betas, eps, wds,
+                          max_norm, losses):
+        """Lockstep fine-tuning of the regions ``tasks`` (smaml_adapt_steps_multi): ``theta`` / ``m`` / ``v``
+        [R, P], ``windows`` [nsteps, R, batch] (host), ``lr_dev`` and ``losses`` [nsteps, R] (device),
+        ``wds`` [R] (host)."""
+        t = np.ascontiguousarray(tasks, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(windows, dtype=np.int32)
+        wd = np.ascontiguousarray(wds, dtype=np.float32).reshape(-1)
+        if w.ndim != 3 or w.shape[1] != t.size or wd.size != t.size:
+            raise ValueError(f"windows {w.shape} / weight decays {wd.shape} do not match {t.size} regions")
+        for name, a, shape in (("theta", theta, None), ("m", m, None), ("v", v, None),
+                               ("lr_dev", lr_dev, (w.shape[0], t.size)), ("losses", losses, (w.shape[0], t.size))):
+            if a.shape[0] != (shape or (t.size,))[0] or (shape and tuple(a.shape) != shape) or not a.is_contiguous():
+                raise ValueError(f"{name} has shape {tuple(a.shape)} (contiguous: {a.is_contiguous()}) for "
+                                 f"{t.size} regions x {w.shape[0]} steps")
+        check(self._L.smaml_adapt_steps_multi(self._h, stream, t.size, t.ctypes.data_as(PI32), ptr(theta), ptr(m),
+                                              ptr(v), int(step0), w.shape[0], w.shape[2], w.ctypes.data_as(PI32),
+                                              ptr(lr_dev), wd.ctypes.data_as(PF32), float(betas[0]), float(betas[1]),
+                                              float(eps), float(max_norm), ptr(losses)))
+
+    def adapt_prepare_multi(self, stream, tasks, batch=1):
+        """adapt_prepare for the regions of a lockstep call: the workspace and every region's feature cache."""
+        t = np.ascontiguousarray(tasks, dtype=np.int32).reshape(-1)
+        check(self._L.smaml_adapt_prepare_multi(self._h, stream, t.size, t.ctypes.data_as(PI32), int(batch)))
 
     def adapt_phases(self):
         """{phase: ms} of the last adapt_steps call (+ 'windows_filled_per_step')."""

@@ -144,6 +144,114 @@ def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_
     return res
 
 
+def lockstep_groups(n_trains) -> List[List[int]]:
+    """Regions that can run in lockstep: equal numbers of training windows (equal step counts per
+    epoch). Groups in order of their first region, regions in order inside a group."""
+    groups = {}
+    for r, n in enumerate(n_trains):
+        groups.setdefault(int(n), []).append(r)
+    return list(groups.values())
+
+
+def check_orders(orders, n_trains, epochs: int) -> List[np.ndarray]:
+    """``orders[r][epoch]``: region r's permutation of its training windows for that epoch, as int32
+    arrays ``[epochs, n_train_r]`` per region. Raises ValueError naming the region on any other shape."""
+    if len(orders) != len(n_trains):
+        raise ValueError(f"orders has {len(orders)} entries for {len(n_trains)} regions")
+    out = []
+    for r, (o, n) in enumerate(zip(orders, n_trains)):
+        try:
+            a = np.asarray(o, np.int32)[:epochs]  # (later epochs' orders may be given and go unused)
+        except ValueError:  # ragged: epochs of different lengths
+            a = np.zeros((0,), np.int32)
+        if a.shape != (epochs, n):
+            raise ValueError(f"orders[{r}] has shape {a.shape}, expected ({epochs}, {n}): one permutation of the "
+                             f"region's {n} training windows per epoch")
+        out.append(a)
+    return out
+
+
+def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, region_names, epochs: int = 15,
+               max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
+               val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
+               dropout_seed: int = 0, orders=None) -> List[AdaptResult]:
+    """``adapt`` for several regions at once (main.py adapts its regions one after another): every region
+    starts from the same meta-trained ``theta`` and keeps its own stream, climate optimiser settings,
+    ``ClimateAwareLRScheduler`` (stepped on its own epoch mean), shuffle orders and Adam state, and each
+    step of all regions of a group runs as one set of launches (``smaml_adapt_steps_multi``). Regions
+    are grouped by their number of training windows (lockstep needs equal step counts); the groups run
+    one after another. Region r computes what ``adapt`` computes on its stream alone.
+    ``orders[r][epoch]``: optional shuffle orders; default: drawn from the global torch RNG region by
+    region, each region's epochs in turn -- the draws of one ``adapt`` call per region in that order."""
+    dev = torch.device(device)
+    R = len(streams)
+    if len(region_names) != R or R == 0:
+        raise ValueError(f"{len(region_names)} region names for {R} streams")
+    ctx = ctx or _capi.Context(dims, dev.index or 0)
+    ei = edge_index.detach().cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
+    ctx.set_graph(ei)
+    gflat = params.pack(gcn, dims, which=1, device=dev)
+    ctx.set_gcn_params(gflat)
+    th0 = params.pack(theta, dims, which=0, device=dev)
+    stream_ts = []
+    for f in streams:
+        t = f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f))
+        stream_ts.append(t.to(dev, torch.float32).contiguous())
+    ctx.set_tasks(stream_ts)
+    ctx.set_task_ids([0] * R)  # every region draws the dropout masks of a single-region adapt()
+    n_maxs = [min(max_samples, synth.num_samples(t.shape[0], dims.window_size, dims.forecast_horizon))
+              for t in stream_ts]
+    n_trains = [int(train_frac * n) for n in n_maxs]
+    if orders is not None:
+        orders = check_orders(orders, n_trains, epochs)
+    else:
+        orders = [np.stack([random_sampler_order(n).numpy().astype(np.int32) for _ in range(epochs)])
+                  if epochs > 0 else np.zeros((0, n), np.int32) for n in n_trains]
+    stream = _capi.stream_ptr(torch)
+    results: List[Optional[AdaptResult]] = [None] * R
+    for group in lockstep_groups(n_trains):
+        G, n_train = len(group), n_trains[group[0]]
+        th = th0.unsqueeze(0).repeat(G, 1).contiguous()
+        m, v = torch.zeros_like(th), torch.zeros_like(th)
+        cfgs = [climate_optimizer_config(region_names[r], base_lr) for r in group]
+        scheds = [ClimateAwareLRScheduler(region_names[r], lr0) for r, (lr0, _) in zip(group, cfgs)]
+        lrs = [lr0 for lr0, _ in cfgs]
+        wds = [wd for _, wd in cfgs]
+        res = [AdaptResult(theta=th[i], n_train=n_train, n_val=n_maxs[r] - n_train) for i, r in enumerate(group)]
+        losses = torch.empty(max(n_train, 1), G, device=dev)
+        ctx.set_dropout(dropout[0], dropout[1], dropout_seed)
+        ctx.adapt_prepare_multi(stream, group, 1)
+        step = 0
+        for ep in range(epochs):
+            ctx.set_dropout(dropout[0], dropout[1], dropout_seed)  # masks keyed by the global step index
+            windows = np.stack([orders[r][ep] for r in group], axis=1).reshape(n_train, G, 1)
+            lr_dev = torch.tensor(lrs, dtype=torch.float32).to(dev).repeat(n_train, 1).contiguous()
+            ctx.adapt_steps_multi(stream, group, th, m, v, step, windows, lr_dev, (0.9, 0.999), 1e-8, wds,
+                                  MAX_GRAD_NORM, losses)
+            step += n_train
+            avgs = losses[:n_train].double().mean(dim=0).cpu().numpy()
+            for i in range(G):
+                res[i].epoch_losses.append(float(avgs[i]))
+                res[i].lrs.append(lrs[i])
+                lrs[i] = scheds[i].step(float(avgs[i]))
+        ctx.set_dropout(0.0, 0.0, 0)
+        for i, r in enumerate(group):
+            res[i].val_loss = evaluate_region(ctx, th[i], r, list(range(n_train, n_maxs[r])), val_batch)
+            results[r] = res[i]
+    return results
+
+
+def evaluate_region(ctx: _capi.Context, theta: torch.Tensor, task: int, sample_ids, batch: int = 32) -> float:
+    """Mean per-sample MSE over the given windows of task ``task`` (no gradients, no dropout): the
+    squared-error sum of ``smaml_forecast`` over the element count."""
+    if len(sample_ids) == 0:
+        return 0.0
+    d = ctx.dims
+    sums = torch.empty(3, d.forecast_horizon, d.output_channels, device=theta.device, dtype=torch.float64)
+    ctx.forecast(_capi.stream_ptr(torch), theta, np.asarray(sample_ids, np.int32), batch, task=task, skill=sums)
+    return float(sums[0].sum().item()) / (len(sample_ids) * d.num_nodes * d.forecast_horizon * d.output_channels)
+
+
 def evaluate(ctx: _capi.Context, theta: torch.Tensor, sample_ids, batch: int = 32) -> float:
     """Mean per-sample MSE over the given windows of task 0 (no gradients, no dropout)."""
     ctx.set_dropout(0.0, 0.0, 0)

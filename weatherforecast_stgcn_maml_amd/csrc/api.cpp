@@ -291,8 +291,13 @@ struct smaml_ctx {
   int bar_fused = 1;                 // smaml_set_option("grid_barrier"): 0 = two launches per kernel
   int bar_oversize = 0;              // smaml_set_option("barrier_oversize"): debug, never co-resident
   uint64_t wall_khz = 0;             // wall_clock64 rate
-  HipBuf ad_F;                     // float [ad_valid.size()][T][N][Hc]
-  std::vector<uint8_t> ad_valid;   // per window start the cache has a slot for
+  struct AdCache {
+    HipBuf F;                    // float [valid.size()][T][N][Hc]
+    std::vector<uint8_t> valid;  // per window start the cache has a slot for
+  };
+  std::vector<AdCache> ad;         // per task of smaml_set_tasks (smaml_adapt_steps uses task 0's)
+  int ad_group = -1;               // smaml_set_option("adapt_group"): regions per lockstep launch set (0: all;
+                                   // -1: the measured plan, ad_group_size)
   int ad_gcn_batch = 32;           // windows per GCN pass when filling the cache (<= 1: one per step)
   int ad_phase_sync = 0;           // smaml_set_option("adapt_phase_sync"): sync at the phase boundaries
   AdPhases ad_ph;                  // host-timed phases of the last smaml_adapt_steps (smaml_adapt_phases)
@@ -355,8 +360,7 @@ void free_keep(smaml_ctx* c) {
 
 // Drops the adaptation feature cache.
 void ad_cache_drop(smaml_ctx* c) {
-  (void)c->ad_F.release();
-  c->ad_valid.clear();
+  c->ad.clear();  // (each slot's buffer is released after a device sync, devbuf.h)
 }
 
 int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
@@ -964,7 +968,9 @@ int run_lstm(smaml_ctx* c, hipStream_t s, const float* theta, int64_t tstride, b
 
 // New graph / GCN parameters / tasks: every cached window is stale, but the slots stay allocated (a
 // re-allocation can cost seconds when the driver has to clear released VRAM, see ad_prepare).
-static void ad_cache_invalidate(smaml_ctx* c) { std::fill(c->ad_valid.begin(), c->ad_valid.end(), (uint8_t)0); }
+static void ad_cache_invalidate(smaml_ctx* c) {
+  for (auto& a : c->ad) std::fill(a.valid.begin(), a.valid.end(), (uint8_t)0);
+}
 
 int run_forward(smaml_ctx* c, hipStream_t s, const float* theta, int64_t tstride, const float* const* xtab_dev,
                 const float* const* first_tab = nullptr) {
@@ -1337,7 +1343,7 @@ extern "C" {
 
 const char* smaml_last_error(void) { return g_err.c_str(); }
 
-int32_t smaml_abi_version(void) { return 8; }
+int32_t smaml_abi_version(void) { return 9; }
 
 const char* smaml_build_info(void) { return smaml::products_info(); }
 
@@ -1882,27 +1888,29 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
 // Z = run-length single-window "tasks" (B = 1), whose [Z][T][N][Hc] output is exactly the run's
 // cache slots. Per-row GCN arithmetic does not depend on how many samples a launch holds, so the
 // features are bitwise those of the per-step fill (the first epoch no longer runs 960 batch-1 GCNs).
-static int ad_cache_fill(smaml_ctx* c, hipStream_t s, const int32_t* windows, int64_t n) {
+// The windows are those of task `task` (its stream, its cache), windows[i * stride] for i < n.
+static int ad_cache_fill(smaml_ctx* c, hipStream_t s, int task, const int32_t* windows, int64_t n, int64_t stride = 1) {
   const Dims& d = c->d;
   const int64_t fsz = (int64_t)d.T * d.N * d.Hc;
+  smaml_ctx::AdCache& ac = c->ad[task];
   std::vector<int32_t> need;
   for (int64_t i = 0; i < n; ++i)
-    if (!c->ad_valid[windows[i]]) need.push_back(windows[i]);
+    if (!ac.valid[windows[i * stride]]) need.push_back(windows[i * stride]);
   if (need.empty()) return SMAML_OK;
   std::sort(need.begin(), need.end());
   need.erase(std::unique(need.begin(), need.end()), need.end());
   std::vector<const float*> ptrs(need.size());
-  for (size_t i = 0; i < need.size(); ++i) ptrs[i] = c->feats[0] + (int64_t)need[i] * d.N * d.Cin0;
+  for (size_t i = 0; i < need.size(); ++i) ptrs[i] = c->feats[task] + (int64_t)need[i] * d.N * d.Cin0;
   TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
   for (size_t i = 0; i < need.size();) {
     size_t j = i + 1;
     while (j < need.size() && need[j] == need[j - 1] + 1 && (int)(j - i) < c->ad_gcn_batch) ++j;
     set_work(c, (int)(j - i), 1);
-    c->w.F = c->ad_F.as<float>() + (int64_t)need[i] * fsz;
+    c->w.F = ac.F.as<float>() + (int64_t)need[i] * fsz;
     const float* const* xt = nullptr;
     TRY(xtab_at(c, (int64_t)i, &xt));
     TRY(run_gcn(c, s, xt));
-    for (size_t k = i; k < j; ++k) c->ad_valid[need[k]] = 1;
+    for (size_t k = i; k < j; ++k) ac.valid[need[k]] = 1;
     i = j;
   }
   return SMAML_OK;
@@ -1914,7 +1922,10 @@ static int ad_cache_fill(smaml_ctx* c, hipStream_t s, const int32_t* windows, in
 // released VRAM that it still has to clear, and that clear otherwise lands in the first kernel that
 // reads the buffer -- i.e. inside the first timed epoch (round 5: 6.1 s of a 6.8 s first epoch on some
 // boxes, 0 on others). Returns with *cache = whether this call's steps use the cache.
-static int ad_prepare(smaml_ctx* c, hipStream_t s, int B, bool* cache_out) {
+// The regions of the call are the `R` tasks `tasks` (smaml_adapt_steps: task 0 alone); the workspace is
+// sized for all R as one launch set. Every region gets a cache of its own stream's length, and *cache is
+// whether all of them have one (a lockstep step reads all its regions' features the same way).
+static int ad_prepare(smaml_ctx* c, hipStream_t s, int B, const int32_t* tasks, int R, bool* cache_out) {
   using clk = std::chrono::steady_clock;
   const Dims& d = c->d;
   auto t0 = clk::now();
@@ -1922,27 +1933,60 @@ static int ad_prepare(smaml_ctx* c, hipStream_t s, int B, bool* cache_out) {
   const int64_t had = c->arena.cap;
   // (the cache fill's GCN passes run ad_gcn_batch windows as tasks: size the workspace for them
   // first, since a growing workspace drops the cache)
-  TRY(reserve(c, fill_batched ? c->ad_gcn_batch : 1, B));
+  if (fill_batched && R < c->ad_gcn_batch) TRY(reserve(c, c->ad_gcn_batch, 1));
+  TRY(reserve(c, R, B));
   if (c->arena.cap != had) {
     HIP_TRY(hipMemsetAsync(c->arena.ptr, 0, (size_t)c->arena.cap, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   auto t1 = clk::now();
   const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
-  const int64_t n = c->t_total.empty() ? 0 : c->t_total[0];
-  bool cache = B == 1 && !(c->p_gcn > 0.f) && n > 0;
-  if (cache && (int64_t)c->ad_valid.size() < n) {  // no cache yet, or a longer stream than it was sized for
-    ad_cache_drop(c);
-    if (c->ad_F.grow_if_room(n * fsz * 4, AD_F_MARGIN)) {
-      c->ad_valid.assign((size_t)n, 0);
-      HIP_TRY(hipMemsetAsync(c->ad_F.ptr, 0, (size_t)(n * fsz * 4), s));
-      HIP_TRY(hipStreamSynchronize(s));
+  if (c->ad.size() < c->feats.size()) c->ad.resize(c->feats.size());
+  bool cache = B == 1 && !(c->p_gcn > 0.f);
+  for (int r = 0; r < R && cache; ++r) {
+    smaml_ctx::AdCache& ac = c->ad[tasks[r]];
+    const int64_t n = c->t_total[tasks[r]];
+    if ((int64_t)ac.valid.size() < n) {  // no cache yet, or a longer stream than it was sized for
+      ac.valid.clear();
+      if (ac.F.grow_if_room(n * fsz * 4, AD_F_MARGIN)) {
+        ac.valid.assign((size_t)n, 0);
+        HIP_TRY(hipMemsetAsync(ac.F.ptr, 0, (size_t)(n * fsz * 4), s));
+        HIP_TRY(hipStreamSynchronize(s));
+      }
     }
+    cache = ac.F.ptr != nullptr && !ac.valid.empty();
   }
   auto t2 = clk::now();
   c->ad_ph.ms[AD_RESERVE] += std::chrono::duration<double, std::milli>(t1 - t0).count();
   c->ad_ph.ms[AD_ALLOC] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-  *cache_out = cache && c->ad_F.ptr;
+  *cache_out = cache;
+  return SMAML_OK;
+}
+
+// Regions per launch set of a lockstep call over R regions (option adapt_group; 0 = all at once). The
+// default (-1) follows the measurement at config-4 shapes: per region, a set of Z
+// regions costs 0.626 ms at Z = 1, 0.60 at 2, 0.80 / 0.65 / 0.66 at 3 / 4 / 5 (the size-based selection
+// leaves the one-launch small-grid kernels there, the big tiles are not yet full), 0.60 at 6, 0.49 at 8,
+// 0.34 at 18 -- so 3 to 5 regions run in sets of 2, every other count all at once.
+static int ad_group_size(const smaml_ctx* c, int R) {
+  if (c->ad_group > 0) return std::min(c->ad_group, R);
+  if (c->ad_group < 0 && R >= 3 && R <= 5) return 2;
+  return std::min(R, ADAPT_MAX_GROUP);
+}
+
+// The regions of a lockstep call: distinct tasks of smaml_set_tasks.
+static int ad_check_tasks(const smaml_ctx* c, const char* who, int32_t nregions, const int32_t* tasks) {
+  if (nregions <= 0 || !tasks) return fail(SMAML_EINVAL, std::string(who) + ": nregions must be positive and tasks_host set");
+  const int nt = (int)c->feats.size();
+  for (int r = 0; r < nregions; ++r) {
+    if (tasks[r] < 0 || tasks[r] >= nt)
+      return fail(SMAML_EINVAL, std::string(who) + ": region " + std::to_string(r) + ": task " + std::to_string(tasks[r]) +
+                                    " out of range (" + std::to_string(nt) + " tasks set)");
+    for (int q = 0; q < r; ++q)
+      if (tasks[q] == tasks[r])
+        return fail(SMAML_EINVAL, std::string(who) + ": duplicate task " + std::to_string(tasks[r]) + " (regions " +
+                                      std::to_string(q) + " and " + std::to_string(r) + ")");
+  }
   return SMAML_OK;
 }
 
@@ -1953,7 +1997,8 @@ int smaml_adapt_prepare(smaml_ctx* c, void* stream, int32_t batch) {
   TRY(ensure_device(c));
   bool cache = false;
   c->ad_ph = AdPhases{};
-  return ad_prepare(c, (hipStream_t)stream, batch, &cache);
+  const int32_t task0 = 0;
+  return ad_prepare(c, (hipStream_t)stream, batch, &task0, 1, &cache);
 }
 
 int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float* v, int32_t step0, int32_t nsteps,
@@ -1977,7 +2022,8 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
   }
   c->ad_ph = AdPhases{};
   bool cache = false;
-  TRY(ad_prepare(c, s, B, &cache));  // no allocation after smaml_adapt_prepare / an earlier call
+  const int32_t task0 = 0;
+  TRY(ad_prepare(c, s, B, &task0, 1, &cache));  // no allocation after smaml_adapt_prepare / an earlier call
   const bool fill_batched = B == 1 && !(c->p_gcn > 0.f) && c->ad_gcn_batch > 1;
   const int64_t P = c->po.P;
   const float inv = 1.f / ((float)d.N * d.HfC * B);
@@ -1987,7 +2033,7 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
   const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
   auto t0 = clk::now();
   if (cache && fill_batched) {
-    TRY(ad_cache_fill(c, s, windows_host, nsteps));
+    TRY(ad_cache_fill(c, s, 0, windows_host, nsteps));
     if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
   }
   auto t1 = clk::now();
@@ -1999,10 +2045,10 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
     if (dropout) set_step_drop(c, step0 + k);
     if (cache) {
       const int wv = windows_host[k];
-      c->w.F = c->ad_F.as<float>() + (int64_t)wv * fsz;
-      if (!c->ad_valid[wv]) {
+      c->w.F = c->ad[0].F.as<float>() + (int64_t)wv * fsz;
+      if (!c->ad[0].valid[wv]) {
         TRY(run_gcn(c, s, xt));  // writes the window's features straight into its cache slot
-        c->ad_valid[wv] = 1;
+        c->ad[0].valid[wv] = 1;
         c->ad_ph.filled += 1;
       }
       TRY(run_lstm(c, s, theta, 0));
@@ -2015,6 +2061,118 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
     TIMED(c, s, C_MISC, 0,
           launch_adam_l2(s, theta, c->grad, m, v, P, c->w.sqpart, lr_dev + k, step0 + k + 1, beta1, beta2, eps,
                          weight_decay, max_norm, c->w.lpart, c->w.lblocks, inv, losses + k));
+  }
+  if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
+  auto t2 = clk::now();
+  c->ad_ph.ms[AD_FILL] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  c->ad_ph.ms[AD_STEPS] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+  c->w.F = c->F_main;
+  c->w.drop = Drop{};
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+int smaml_adapt_prepare_multi(smaml_ctx* c, void* stream, int32_t nregions, const int32_t* tasks_host, int32_t batch) {
+  TRY(require_ready(c));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (batch <= 0) return fail(SMAML_EINVAL, "bad adapt_prepare_multi batch");
+  TRY(ad_check_tasks(c, "adapt_prepare_multi", nregions, tasks_host));
+  TRY(ensure_device(c));
+  bool cache = false;
+  c->ad_ph = AdPhases{};
+  return ad_prepare(c, (hipStream_t)stream, batch, tasks_host, nregions, &cache);
+}
+
+// R regions' fine-tuning in lockstep: step k of every region of a group as ONE set of launches over the
+// task axis (Z = the group's regions, per-task parameters at stride P), as the MAML inner loop runs its
+// tasks. The regions of a group are consecutive entries of tasks_host, so their theta / m / v / lr /
+// loss slabs are the caller's arrays at the group's offset. With the feature cache, the step's R slots
+// (one per region, anywhere in that region's cache) are gathered into the workspace's contiguous F by one
+// copy launch from a device table of slot pointers uploaded with the window table (k_gather_slabs).
+int smaml_adapt_steps_multi(smaml_ctx* c, void* stream, int32_t nregions, const int32_t* tasks_host, float* theta,
+                            float* m, float* v, int32_t step0, int32_t nsteps, int32_t batch,
+                            const int32_t* windows_host, const float* lr_dev, const float* weight_decay_host,
+                            float beta1, float beta2, float eps, float max_norm, float* losses) {
+  using clk = std::chrono::steady_clock;
+  TRY(require_ready(c));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !m || !v || nsteps <= 0 || batch <= 0 || !windows_host || !lr_dev || !weight_decay_host || !losses ||
+      step0 < 0)
+    return fail(SMAML_EINVAL, "bad adapt_steps_multi arguments");
+  TRY(ad_check_tasks(c, "adapt_steps_multi", nregions, tasks_host));
+  TRY(ensure_device(c));
+  hipStream_t s = (hipStream_t)stream;
+  const Dims& d = c->d;
+  const int B = batch, R = nregions;
+  const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
+  // one table for the call: the window pointers [nsteps][R][B], then the cache-slot pointers [nsteps][R]
+  const int64_t nwin = (int64_t)nsteps * R * B, nslot = (int64_t)nsteps * R;
+  std::vector<const float*> ptrs(nwin + nslot, nullptr);
+  for (int64_t i = 0; i < nwin; ++i) {
+    const int r = (int)(i / B % R), task = tasks_host[r];
+    const int wv = windows_host[i];
+    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[task])
+      return fail(SMAML_EINVAL, "adapt_steps_multi: region " + std::to_string(r) + " (task " + std::to_string(task) +
+                                    "): window " + std::to_string(wv) + " of step " + std::to_string(i / B / R) +
+                                    " out of range (stream of " + std::to_string(c->t_total[task]) + " rows)");
+    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
+  }
+  c->ad_ph = AdPhases{};
+  bool cache = false;
+  TRY(ad_prepare(c, s, B, tasks_host, R, &cache));  // no allocation after smaml_adapt_prepare_multi / an earlier call
+  const int G = ad_group_size(c, R);  // regions per launch set
+  const int64_t P = c->po.P;
+  const float inv = 1.f / ((float)d.N * d.HfC * B);
+  const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
+  if (dropout) {  // masks keyed by each region's task id (smaml_set_task_ids; default: the task index)
+    std::vector<int32_t> ids(R);
+    for (int r = 0; r < R; ++r) ids[r] = tasks_host[r] < (int)c->task_ids.size() ? c->task_ids[tasks_host[r]] : tasks_host[r];
+    TRY(c->stage.upload(s, c->task_id_dev, ids.data(), (int64_t)R * 4));
+  }
+  auto t0 = clk::now();
+  if (cache) {
+    // every region's missing windows up front, region by region (cache is on only at B = 1: [nsteps][R])
+    for (int r = 0; r < R; ++r) TRY(ad_cache_fill(c, s, tasks_host[r], windows_host + r, nsteps, R));
+    if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < nslot; ++i)
+      ptrs[nwin + i] = c->ad[tasks_host[i % R]].F.as<float>() + (int64_t)windows_host[i] * fsz;
+  }
+  auto t1 = clk::now();
+  TRY(upload_xtab(c, s, ptrs.data(), nwin + nslot));
+  for (int k = 0; k < nsteps; ++k) {
+    for (int r0 = 0; r0 < R; r0 += G) {
+      const int Z = std::min(G, R - r0);
+      set_work(c, Z, B);
+      // (one region: the parameters at stride 0, as smaml_adapt_steps passes them)
+      float* th = theta + (int64_t)r0 * P;
+      const int64_t ts = Z > 1 ? P : 0;
+      const float* const* xt = nullptr;
+      TRY(xtab_at(c, ((int64_t)k * R + r0) * B, &xt));
+      if (dropout) {
+        set_step_drop(c, step0 + k);
+        c->w.drop.task_id = c->task_id_dev + r0;
+      }
+      if (cache) {
+        if (Z == 1) {
+          c->w.F = const_cast<float*>(ptrs[nwin + (int64_t)k * R + r0]);  // the slot itself
+        } else {
+          const float* const* st = nullptr;
+          TRY(xtab_at(c, nwin + (int64_t)k * R + r0, &st));
+          TIMED(c, s, C_GCN, 0, launch_gather_slabs(s, st, Z, fsz, c->F_main));
+        }
+        TRY(run_lstm(c, s, th, ts));
+      } else {
+        TRY(run_forward(c, s, th, ts, xt));
+      }
+      TIMED(c, s, C_HEAD, 2.0 * Z * c->w.M * d.HfC * d.H, launch_head_loss(s, d, c->w, th, ts, c->po, xt, 2.f * inv, true));
+      TRY(run_backward(c, s, th, ts, c->grad));
+      AdamWd wds{};
+      for (int z = 0; z < Z; ++z) wds.wd[z] = weight_decay_host[r0 + z];
+      TIMED(c, s, C_MISC, 0,
+            launch_adam_l2_multi(s, th, c->grad, m + (int64_t)r0 * P, v + (int64_t)r0 * P, P, Z, c->w.sqpart,
+                                 lr_dev + (int64_t)k * R + r0, step0 + k + 1, beta1, beta2, eps, wds, max_norm,
+                                 c->w.lpart, c->w.lblocks, inv, losses + (int64_t)k * R + r0));
+    }
   }
   if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
   auto t2 = clk::now();
@@ -2111,6 +2269,8 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->kn.fwd_streams = (int)value;
   } else if (k == "adapt_phase_sync" && (value == 0 || value == 1)) {
     c->ad_phase_sync = (int)value;
+  } else if (k == "adapt_group" && value >= -1 && value <= ADAPT_MAX_GROUP) {
+    c->ad_group = (int)value;
   } else if (k == "adapt_gcn_batch" && value >= 0 && value <= 256) {
     c->ad_gcn_batch = (int)value;
   } else if (k == "wgrad_group_wgs" && value >= 1) {

@@ -595,6 +595,21 @@ void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v,
                     const float* lr_dev, int step, float b1, float b2, float eps, float wd, float max_norm,
                     const float* lpart, int lblocks, float inv_count, float* loss);
 
+// launch_adam_l2 for R regions in lockstep (smaml_adapt_steps_multi), region r on blockIdx.y: p, g, m, v
+// [R][n], part [R][SQB], lr_dev [R], lpart [R][lblocks], loss [R]; each region clips by its own norm,
+// steps at its own learning rate and weight decay and sums its own loss. Element arithmetic and the
+// host-computed bias corrections are launch_adam_l2's.
+constexpr int ADAPT_MAX_GROUP = 64;  // regions per launch set (the weight decays travel as a kernel argument)
+struct AdamWd {
+  float wd[ADAPT_MAX_GROUP];
+};
+void launch_adam_l2_multi(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, int R, double* part,
+                          const float* lr_dev, int step, float b1, float b2, float eps, const AdamWd& wd,
+                          float max_norm, const float* lpart, int lblocks, float inv_count, float* loss);
+// dst [Z][n] <- tab[z][0 .. n) (device table of Z source pointers): the lockstep step's features, one
+// cache slot per region, into the workspace's contiguous F
+void launch_gather_slabs(hipStream_t s, const float* const* tab, int Z, int64_t n, float* dst);
+
 // ---- second-order launchers (kernels_dual.hip) ----
 void launch_lstm_fwd_dual_wave(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
                                const float* U, int64_t tstride, const ParamOff& po, double* flops, int chunk = 0,

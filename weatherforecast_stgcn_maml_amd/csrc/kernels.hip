@@ -2820,6 +2820,81 @@ void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v,
                               lpart, lblocks, inv_count, loss);
 }
 
+// k_adam_l2 for R regions adapted in lockstep, region r = blockIdx.y: its own parameter / moment / gradient
+// slabs, clip coefficient (its SQB partials), learning rate, weight decay and loss (its head partials,
+// summed in k_adam_l2's order). The element arithmetic is k_adam_l2's, expression for expression, so a
+// region computes bitwise what the single-region kernel computes from the same inputs.
+__global__ void k_adam_l2_multi(float* __restrict__ p_all, const float* __restrict__ g_all, float* __restrict__ m_all,
+                                float* __restrict__ v_all, int64_t n, const double* __restrict__ part_all,
+                                const float* __restrict__ lr_dev, double bc1, float bc2_sqrt, float b1, float b2,
+                                float eps, AdamWd wds, float max_norm, const float* __restrict__ lpart_all,
+                                int lblocks, float inv_count, float* __restrict__ loss) {
+  const int r = blockIdx.y;
+  float* __restrict__ p = p_all + (int64_t)r * n;
+  const float* __restrict__ g = g_all + (int64_t)r * n;
+  float* __restrict__ m = m_all + (int64_t)r * n;
+  float* __restrict__ v = v_all + (int64_t)r * n;
+  if (loss && blockIdx.x == 0) {
+    __shared__ float red[NT / 64];
+    const float* lpart = lpart_all + (int64_t)r * lblocks;
+    float a = 0.f;
+    for (int i = threadIdx.x; i < lblocks; i += NT) a += lpart[i];
+    const float s = block_sum(a, red);
+    if (threadIdx.x == 0) loss[r] = s * inv_count;
+  }
+  float total;
+  const float coef = clip_coef_from(part_all + (int64_t)r * SQB, max_norm, &total);
+  const float lr = lr_dev[r];
+  const float wd = wds.wd[r];
+  const float step_size = (float)((double)lr / bc1);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float gi = fmaf(wd, p[i], g[i] * coef);
+    const float mi = m[i] + (1.f - b1) * (gi - m[i]);
+    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    p[i] = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+// (two launches, as launch_adam_l2: see the measurement above it)
+void launch_adam_l2_multi(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, int R, double* part,
+                          const float* lr_dev, int step, float b1, float b2, float eps, const AdamWd& wd,
+                          float max_norm, const float* lpart, int lblocks, float inv_count, float* loss) {
+  int nb = (int)((n + NT - 1) / NT);
+  if (nb > 2048) nb = 2048;
+  k_sqsum<<<dim3(SQB, R), NT, 0, s>>>(g, n, part);
+  const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
+  k_adam_l2_multi<<<dim3(nb, R), NT, 0, s>>>(p, g, m, v, n, part, lr_dev, bc1, (float)std::sqrt(bc2), b1, b2, eps, wd,
+                                             max_norm, lpart, lblocks, inv_count, loss);
+}
+
+// dst [Z][n] <- tab[z][0 .. n): 16-byte copies when n and every pointer allow it (vec), else by element.
+__global__ void k_gather_slabs(const float* const* __restrict__ tab, int64_t n, float* __restrict__ dst, int vec) {
+  const int z = blockIdx.y;
+  const float* __restrict__ src = tab[z];
+  float* __restrict__ out = dst + (int64_t)z * n;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, st = (int64_t)gridDim.x * blockDim.x;
+  if (vec) {
+    const int64_t n4 = n >> 2;
+    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+    float4* __restrict__ o4 = reinterpret_cast<float4*>(out);
+    for (int64_t i = i0; i < n4; i += st) o4[i] = s4[i];
+  } else {
+    for (int64_t i = i0; i < n; i += st) out[i] = src[i];
+  }
+}
+
+// (vec is decided by the caller's layout: n % 4 == 0 and slots at multiples of n floats from 256-byte-aligned
+// bases, which holds for every cache slot and for the workspace's F)
+void launch_gather_slabs(hipStream_t s, const float* const* tab, int Z, int64_t n, float* dst) {
+  const int vec = n % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+  const int64_t items = vec ? n / 4 : n;
+  int nb = (int)std::min<int64_t>((items + NT - 1) / NT, 1024);
+  if (nb < 1) nb = 1;
+  k_gather_slabs<<<dim3(nb, Z), NT, 0, s>>>(tab, n, dst, vec);
+}
+
 }  // namespace smaml
 
 namespace smaml {
