@@ -173,8 +173,52 @@ int smaml_set_tasks(smaml_ctx* ctx, int32_t ntasks, const float* const* features
 int smaml_forecast(smaml_ctx* ctx, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
                    int32_t nwin, int32_t batch, const float* scale_host, float* pred, double* skill);
 
-/* Bytes of device memory the forecast's own buffers hold (not part of smaml_workspace_bytes). */
+/* Bytes of device memory the forecast's own buffers hold (not part of smaml_workspace_bytes; those of
+ * smaml_forecast_ensemble included). */
 int64_t smaml_forecast_bytes(const smaml_ctx* ctx);
+
+/* MC-dropout ensemble forecast: `members` (E, 1..64) stochastic forwards per window, in lockstep over the
+ * member axis, with the ensemble mean, spread and probabilistic scores. Windows, passes, alignment and
+ * range errors as smaml_forecast. Member e of window i (position in windows_host) is what
+ * HybridSTGCN_LSTM.train()'s forward under no_grad computes for that window with this library's
+ * counter-based masks (kernels.h Drop; oracle/refcpu.py Dropout):
+ *   Masks: member e uses the sites drop_site(seed, kind, step = e, layer) with task id 0. The probabilities
+ *   (p_gcn: after conv1..conv3; p_lstm: between LSTM layers and on the head input; each in [0, 1), 0 = that
+ *   site off) and the seed are this call's arguments: the state of smaml_set_dropout / smaml_set_task_ids
+ *   is neither read nor changed.
+ *   Element indices are those of the training forward of ONE batch holding the whole window list:
+ *   B := nwin, sample b := i, M := nwin*N, row m := i*N + n:
+ *     kind 1, layer k:  ((0*nwin + i) * T*N + row) * Hc + ch      (row = t*N + n of the window)
+ *     kind 2, layer l:  ((0*T + t) * nwin*N + i*N + n) * H + unit
+ *     kind 3:           (i*N + n) * H + unit
+ *   so a member does not depend on `batch`, on how the list is cut into passes or on the grouping below, and
+ *   refcpu.batch_loss(Pt, Pg, task, windows, refcpu.Dropout(seed, p_gcn, p_lstm, 0, e)) is member e's oracle.
+ *   SMAML_EINVAL (with a message): members outside 1..64; a probability outside [0, 1); mean, spread,
+ *   member_pred and scores all NULL; scores requested for a window without targets; smaml_forecast's errors.
+ *   member_pred (device, optional) [members][nwin][N*Hf][C]: normalised predictions, rows n*Hf + h.
+ *   mean, spread (device, optional) [nwin][N*Hf][C]: the member sum in member order divided by E; the
+ *   unbiased standard deviation about that mean (two-pass), 0 when E = 1.
+ *   scores (device doubles, optional) [4][Hf][C], overwritten: sums over windows and nodes with the F4
+ *   pairing, y, y_last and s_c = scale_host[c] exactly as smaml_forecast's skill sums:
+ *     [0] sum (s (mu - y))^2          the error of the ensemble mean
+ *     [1] sum s^2 sigma^2             the unbiased ensemble variance
+ *     [2] sum s CRPS,  CRPS = (1/E) sum_i |x_i - y| - (1/(2 E^2)) sum_{i,j} |x_i - x_j|
+ *                                     (formed as (1/E^2) sum_{i<j}, the pairs in lexicographic order)
+ *     [3] sum (s (y_last - y))^2      persistence
+ *   Fixed order: f32 per block, double across blocks and passes. Bitwise repeatable.
+ * What does not depend on the masks runs once per pass: with p_gcn == 0 the GCN features and layer 0's input
+ * projection (per distinct stream row on consecutive windows, as smaml_forecast) and layer 0 of the LSTM
+ * itself when a layer above reads it, i.e. with two or more LSTM layers (option ens_share, default 1; 0
+ * computes it per member: bitwise the same members; a one-layer LSTM always does). With p_gcn > 0
+ * every member runs its own GCN. Members run ens_group at a time (option; 0 = all, default -1 = the largest
+ * group whose rings and per-member features fit 2 GiB); any grouping gives bitwise the same result.
+ * State isolation as smaml_forecast: the buffers are the forecast's own (grow only, in smaml_forecast_bytes),
+ * smaml_workspace_bytes, the adaptation feature cache and the meta-step state are untouched, and a pending
+ * smaml_forward / smaml_backward pair stays valid across the call. */
+int smaml_forecast_ensemble(smaml_ctx* ctx, void* stream, const float* theta, int32_t task,
+                            const int32_t* windows_host, int32_t nwin, int32_t batch, int32_t members, float p_gcn,
+                            float p_lstm, uint32_t seed, const float* scale_host, float* mean, float* spread,
+                            float* member_pred, double* scores);
 
 /* One meta-step over all registered tasks (meta_update_v4, train_hybrid_maml_v5.py:144-184,
  * wrapping inner_loop_v4, :110-141):
@@ -343,7 +387,8 @@ int smaml_timing_collect(smaml_ctx* ctx, double* ms, double* flops, int64_t* cou
  * kernels.h enum Variant (_capi.VARIANTS): fwd, fwd_drop, fwd_split, fwd_img, fwd_dual,
  * fwd_dual_kept, fwd_dual_img, bwd_big, bwd_small, bwd_split, bwd_dual_big, bwd_dual_big_kept,
  * bwd_dual_small, bwd_dual_small_kept, wgrad, wgrad_wide, wgrad_pair, fwd_kw, bwd_kw, gcn_dedup,
- * xg_dedup, wgrad_dedup, f_compact, fwd_infer (smaml_forecast's inference step).
+ * xg_dedup, wgrad_dedup, f_compact, fwd_infer (smaml_forecast's inference step), fwd_infer_drop
+ * (smaml_forecast_ensemble's: one launch per diagonal and member group).
  * Writes min(cap, count) entries, *count = number of variants; reset != 0 zeroes them. Host-side
  * counters: no synchronisation. Lets tests assert which configurations ran. */
 int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count, int32_t reset);
@@ -384,6 +429,11 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  runs of up to this many consecutive missing windows per GCN pass
  *                                  (default 32; 0 or 1 = one window per step as it is first read;
  *                                  bitwise equal);
+ *   "ens_share":                   smaml_forecast_ensemble with p_gcn = 0 runs layer 0 of the LSTM once for
+ *                                  all members (default 1; 0 = per member; bitwise equal);
+ *   "ens_group":                   smaml_forecast_ensemble runs its members this many at a time (0: all at
+ *                                  once; at most 64; -1, the default: the largest group whose rings and
+ *                                  per-member features fit 2 GiB; bitwise equal);
  *   "adapt_group":                 smaml_adapt_steps_multi runs its regions this many at a time, each group
  *                                  as one set of launches per step (0: all at once; at most 64; -1, the
  *                                  default: the measured plan -- 3 to 5 regions in sets of 2, where a set

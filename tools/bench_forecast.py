@@ -13,7 +13,14 @@ the timed repetitions one more repetition per arm runs with the per-category eve
 Prints the arms' median and min-max, windows/s, the ratio to the yardstick, smaml_forecast_bytes against
 smaml_workspace_bytes, the per-category kernel times, and ONE JSON line last.
 
-Usage: python tools/bench_forecast.py [--reps 5] [--warmup 1] [--windows 1200]
+With --members E the tool times the MC-dropout ensemble (smaml_forecast_ensemble) instead: E members over the
+same windows in passes of --batch (32), scores only, in four arms -- p_gcn = 0 (features, layer 0's projection
+and LSTM layer 0 shared by the members) and p_gcn = 0.2 (per-member GCN), each with option ens_share 1 and 0 --
+against the arm `deterministic`: smaml_forecast of the same windows at the same pass size in the same run,
+whose median times E is the yardstick (E separate eval forecasts). p_lstm = 0.2 throughout. Optional
+--group G sets option ens_group for every ensemble arm.
+
+Usage: python tools/bench_forecast.py [--reps 5] [--warmup 1] [--windows 1200] [--members E [--batch 32] [--group G]]
 """
 from __future__ import annotations
 
@@ -34,6 +41,9 @@ def main():
     p.add_argument("--reps", type=int, default=5, help="timed repetitions per arm (>= 5 for the spread)")
     p.add_argument("--warmup", type=int, default=1, help="untimed repetitions per arm first")
     p.add_argument("--windows", type=int, default=1200)
+    p.add_argument("--members", type=int, default=0, help="time the E-member ensemble instead (see above)")
+    p.add_argument("--batch", type=int, default=32, help="--members: windows per pass")
+    p.add_argument("--group", type=int, default=-1, help="--members: option ens_group (-1: the default plan)")
     a = p.parse_args()
     import torch
 
@@ -61,6 +71,8 @@ def main():
         ctx.set_tasks([stream_t])
         return ctx
 
+    if a.members > 0:
+        return ensemble_main(a, d, context, theta, windows, st, torch)
     fc_ctx, ms_ctx = context(), context()
     sums = torch.zeros(3, d.forecast_horizon, d.output_channels, device=dev, dtype=torch.float64)
     out = {}
@@ -127,6 +139,85 @@ def main():
         "value": res["forecast_32"]["windows_per_s"], "unit": "windows/s", "higher_is_better": True,
         "windows": a.windows, "reps": a.reps, "warmup": a.warmup, "arms": res,
         "forecast_bytes_pass32": fb32, "forecast_bytes": fb, "yardstick_workspace_bytes": wb,
+        "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
+
+
+def ensemble_main(a, d, context, theta, windows, st, torch):
+    E, B = a.members, a.batch
+    dev = theta.device
+    skill = torch.zeros(3, d.forecast_horizon, d.output_channels, device=dev, dtype=torch.float64)
+    scores = torch.zeros(4, d.forecast_horizon, d.output_channels, device=dev, dtype=torch.float64)
+    out = {}
+    det_ctx = context()
+
+    def det():
+        det_ctx.forecast(st, theta, windows, B, skill=skill)
+        torch.cuda.synchronize()
+        out["deterministic"] = skill.cpu().numpy()
+
+    arms = {"deterministic": (det, det_ctx)}
+    for p_gcn in (0.0, 0.2):
+        for share in (1, 0):
+            ctx = context()
+            ctx.set_option("ens_share", share)
+            ctx.set_option("ens_group", a.group)
+
+            def run(ctx=ctx, p_gcn=p_gcn, key=f"ens_pgcn{p_gcn:g}_share{share}"):
+                ctx.forecast_ensemble(st, theta, windows, B, E, p_gcn, 0.2, 12345, scores=scores)
+                torch.cuda.synchronize()
+                out[key] = scores.cpu().numpy()
+
+            arms[f"ens_pgcn{p_gcn:g}_share{share}"] = (run, ctx)
+    times = {k: [] for k in arms}
+    for _ in range(a.warmup):
+        for fn, _ in arms.values():
+            fn()
+    for _ in range(a.reps):
+        for k, (fn, _) in arms.items():  # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    cats = {}
+    for k, (fn, ctx) in arms.items():
+        ctx.timing(True)
+        ctx.timing_collect()
+        fn()
+        cats[k] = {c: v for c, v in ctx.timing_collect().items() if v["launches"]}
+        ctx.timing(False)
+    for k, v in out.items():
+        assert np.isfinite(v).all(), k
+    for p_gcn in ("0", "0.2"):  # sharing changes no bit
+        assert np.array_equal(out[f"ens_pgcn{p_gcn}_share1"], out[f"ens_pgcn{p_gcn}_share0"]), p_gcn
+    # the persistence sums are the deterministic forecast's (same targets, same blocks)
+    assert np.allclose(out["ens_pgcn0_share1"][3], out["deterministic"][2], rtol=1e-6)
+    res = {}
+    for k, ts in times.items():
+        ms = np.asarray(ts) * 1e3
+        res[k] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+    yard = E * res["deterministic"]["median_ms"]
+    print(f"{E} members, {a.windows} windows in passes of {B}, ens_group {a.group}, {a.reps} reps after {a.warmup} warm-up")
+    for k, r in res.items():
+        line = f"{k:22s} median {r['median_ms']:9.1f} ms  (min {r['min_ms']:.1f} - max {r['max_ms']:.1f})"
+        if k != "deterministic":
+            r["vs_E_x_deterministic"] = r["median_ms"] / yard
+            line += f"  = {r['vs_E_x_deterministic']:.3f} x ({E} x deterministic = {yard:.1f} ms)"
+        print(line)
+    for p_gcn in ("0", "0.2"):
+        on, off = res[f"ens_pgcn{p_gcn}_share1"], res[f"ens_pgcn{p_gcn}_share0"]
+        print(f"p_gcn {p_gcn}: ens_share 1 / ens_share 0 = {on['median_ms'] / off['median_ms']:.3f} "
+              f"(ranges {'overlap' if on['max_ms'] >= off['min_ms'] and off['max_ms'] >= on['min_ms'] else 'do not overlap'})")
+    fbytes = {k: ctx.forecast_bytes() for k, (_, ctx) in arms.items()}
+    for k, b in fbytes.items():
+        print(f"smaml_forecast_bytes {k}: {b} ({b / 2**20:.0f} MiB)")
+    for k, c in cats.items():
+        print(f"{k} kernel ms by category: " + ", ".join(f"{n} {v['ms']:.1f} ({v['launches']})" for n, v in c.items()))
+    best = res["ens_pgcn0_share1"]
+    print(json.dumps({
+        "metric": f"{E}-member MC-dropout ensemble + scores, member-windows/sec (N=441, T=24, config-2 dims, p_gcn=0)",
+        "value": E * a.windows / (best["median_ms"] * 1e-3), "unit": "member-windows/s", "higher_is_better": True,
+        "members": E, "windows": a.windows, "batch": B, "ens_group": a.group, "reps": a.reps, "warmup": a.warmup,
+        "arms": res, "forecast_bytes": fbytes,
         "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
 
 

@@ -25,7 +25,7 @@ EXPORTS = (
     "smaml_comm_init", "smaml_comm_allreduce", "smaml_comm_destroy", "smaml_variant_counts", "smaml_set_option",
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
-    "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi",
+    "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -33,7 +33,7 @@ GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
 # kernels.h enum Variant: launch counters per kernel tile configuration (smaml_variant_counts)
 VARIANTS = ("fwd", "fwd_drop", "fwd_split", "fwd_img", "fwd_dual", "fwd_dual_kept", "fwd_dual_img", "bwd_big", "bwd_small", "bwd_split",
             "bwd_dual_big", "bwd_dual_big_kept", "bwd_dual_small", "bwd_dual_small_kept", "wgrad", "wgrad_wide", "wgrad_pair",
-            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact", "fwd_infer")
+            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact", "fwd_infer", "fwd_infer_drop")
 
 # api.cpp enum Cat: one kernel per category (the bench's roofline kernel is one symbol)
 TIMING_CATEGORIES = ("gcn_layer", "lstm_fwd_step", "lstm_fwd_dual", "head_loss", "head_dh", "lstm_bwd_step",
@@ -122,6 +122,7 @@ _SIGS = {
     "smaml_forecast_bytes": ([P], I64),
     "smaml_adapt_steps_multi": ([P, P, I32, PI32, P, P, P, I32, I32, I32, PI32, P, PF32, F32, F32, F32, F32, P], I32),
     "smaml_adapt_prepare_multi": ([P, P, I32, PI32, I32], I32),
+    "smaml_forecast_ensemble": ([P, P, P, I32, PI32, I32, I32, I32, F32, F32, ctypes.c_uint32, PF32, P, P, P, P], I32),
 }
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
@@ -357,6 +358,22 @@ class Context:
                                      sc.ctypes.data_as(PF32) if sc is not None else None,
                                      ptr(pred) if pred is not None else None,
                                      ptr(skill) if skill is not None else None))
+
+    def forecast_ensemble(self, stream, theta, windows, batch, members, p_gcn, p_lstm, seed, task=0, scale=None,
+                          mean=None, spread=None, member_pred=None, scores=None):
+        """MC-dropout ensemble of ``members`` stochastic forwards per window (smaml_forecast_ensemble): member
+        ``e`` under the masks of ``(seed, step e)``. Device tensors, each optional: ``mean`` / ``spread``
+        [nwin, N*Hf, C], ``member_pred`` [members, nwin, N*Hf, C] float32, ``scores`` [4, Hf, C] float64
+        (``forecast.ENSEMBLE_SUMS``; ``scale`` = their per-variable factors, host, [C])."""
+        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+        if sc is not None and sc.size != self.dims.output_channels:
+            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
+        check(self._L.smaml_forecast_ensemble(
+            self._h, stream, ptr(theta), int(task), w.ctypes.data_as(PI32), w.size, int(batch), int(members),
+            float(p_gcn), float(p_lstm), int(seed) & 0xFFFFFFFF, sc.ctypes.data_as(PF32) if sc is not None else None,
+            opt(mean), opt(spread), opt(member_pred), opt(scores)))
 
     def forecast_bytes(self):
         return int(self._L.smaml_forecast_bytes(self._h))

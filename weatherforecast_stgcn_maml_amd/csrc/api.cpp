@@ -330,6 +330,13 @@ struct smaml_ctx {
   HipBuf fc_pred;           // [M][HfC]
   HipBuf fc_part;           // [skill_blocks][HfC][3]
   HipBuf fc_scale;          // [C]
+  // smaml_forecast_ensemble shares the buffers above (fc_part holds 4 sums per entry there) and adds the
+  // members' rings and the pass's member predictions
+  HipBuf ens_ring;          // float [2][L][2][G][M][H], G = members per launch set
+  HipBuf ens_pred;          // [E][M][HfC]
+  bool ens_lds_set = false; // k_ens_stats's dynamic-LDS limit raised on this context's device (ens_stats_prepare)
+  int ens_share = 1;        // smaml_set_option("ens_share"): layer 0 of the LSTM once for all members (p_gcn = 0)
+  int ens_group = -1;       // smaml_set_option("ens_group"): members per launch set (0: all; -1: ens_group_size)
   // side streams of the row-chunked BPTT (knob bptt_streams) and their fork / join events
   hipStream_t cs[4] = {};
   hipEvent_t fork_ev = nullptr, join_ev[4] = {};
@@ -1286,6 +1293,157 @@ int forecast_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
   return SMAML_OK;
 }
 
+// ---- smaml_forecast_ensemble: MC-dropout members in lockstep ------------------------------------------
+// Members of one launch set for a pass of M rows: `want` (option ens_group; 0 = all), else the largest
+// group whose rings -- and, with GCN dropout, per-member features -- stay within ENS_GROUP_BUDGET.
+constexpr int64_t ENS_GROUP_BUDGET = 2ll << 30;
+int ens_group_size(const Dims& d, int M, int E, bool per_member_F, int want) {
+  if (want > 0) return std::min(want, E);
+  if (want == 0) return E;
+  const int64_t per = 2 * infer_ring_floats(d, 1, M) * 4 + (per_member_F ? (int64_t)d.T * M * d.Hc * 4 : 0);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(E, ENS_GROUP_BUDGET / per));
+}
+
+struct EnsArgs {
+  int E = 0;
+  float p_gcn = 0.f, p_lstm = 0.f;
+  uint32_t seed = 0;
+  int64_t done = 0, nwin = 0;  // this pass's first window in the call's list, and the list's length
+};
+
+// One pass of B windows for all E members (forecast_pass's counterpart). p_gcn == 0: the GCN features and
+// layer 0's projection once for all members (forecast_pass's own dedup and compact layout), layer 0 of the
+// LSTM once (option ens_share), layers >= 1 with grid z = member. p_gcn > 0: each member's GCN on the
+// per-layer launchers, masked in place after conv1..conv3 (kind 1), into its own F. The members'
+// predictions go to c->ens_pred [E][B][N*Hf][C], from which k_ens_stats forms every output.
+int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
+                  const EnsArgs& a, const float* scale_dev, float* mean, float* spread, float* member_pred,
+                  double* scores) {
+  const Dims& d = c->d;
+  const Knobs& kn = c->kn;
+  const int M = B * d.N, E = a.E;
+  const bool shared = a.p_gcn == 0.f;
+  const int G = ens_group_size(d, M, E, !shared, c->ens_group);
+  const bool dedup_gcn = shared && consec && kn.gcn_dedup && B > 1;
+  const bool fused = shared && gcn_mlp_supported(d) && kn.gcn_fused;
+  const bool want_xg = shared && consec && kn.xg_dedup && B > 1;
+  const int64_t xrows = xg_dedup_rows(B, d.T, d.N);
+  const bool have_xg = want_xg && c->fc_xg.grow(xrows * 4 * d.H * 4) == hipSuccess;
+  const bool compact = shared && forecast_compact_ok(c, consec, B, have_xg);
+  const int64_t grows = fused       ? (int64_t)M
+                        : dedup_gcn ? std::max<int64_t>((int64_t)(B + d.T - 1) * d.N, M)
+                                    : (int64_t)d.T * M;
+  const int64_t ring = infer_ring_floats(d, G, M);
+  const int64_t fslab = (int64_t)d.T * M * d.Hc;  // floats of one member's own features
+  if (c->ens_ring.grow(2 * ring * 4) != hipSuccess ||
+      c->fc_F.grow((shared ? (compact ? xrows * d.Hc : fslab) : G * fslab) * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, grows * d.Hc * 4}, {&c->fc_gcnB, grows * d.Hc * 4}}) != hipSuccess ||
+      c->ens_pred.grow((int64_t)E * M * d.HfC * 4) != hipSuccess ||
+      (scores && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 4 * 4) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the ensemble buffers failed (batch " + std::to_string(B) + ", " +
+                                  std::to_string(G) + " members at a time)");
+  Work w{};
+  w.Z = 1;
+  w.B = B;
+  w.M = M;
+  w.F = c->fc_F.as<float>();
+  w.gcnA = c->fc_gcnA.as<float>();
+  w.gcnB = c->fc_gcnB.as<float>();
+  w.vcount = c->vcount;
+  w.kn = kn;
+  c->w = w;
+  if (shared) TRY(run_gcn(c, s, xt, consec ? xt : nullptr, compact ? 1 : 0));
+  TRY(prep_gate_images(c, s, theta, 0));
+  Work& cw = c->w;
+  if (have_xg) {
+    XgDedup xd{};
+    xd.zstride = xrows * 4 * d.H;
+    xd.N = d.N;
+    cw.xgd = xd;  // (zstride read by the launcher)
+    float* dst = c->fc_xg.as<float>();
+    const bool img = cw.gimg.th && cw.gimg_src == theta;
+    TIMED(c, s, C_XG, 2.0 * xrows * 4 * d.H * c->po.lay[0].cin,
+          launch_xg_dedup(s, d, cw, theta, 0, c->po, img ? cw.gimg.th : nullptr, cw.gimg.tstride, cw.gimg.off[0][0],
+                          dst));
+    xd.xg = dst;
+    xd.src = theta;
+    cw.xgd = xd;
+  }
+  EnsDrop ed{};
+  ed.seed = a.seed;
+  ed.thr = (uint32_t)std::lround((double)a.p_lstm * 16777216.0);
+  ed.sc = 1.f / (1.f - a.p_lstm);
+  ed.row0 = a.done * d.N;
+  ed.Mtot = a.nwin * d.N;
+  // (a one-layer LSTM has no layer above to read a shared layer 0: its layer 0 is the top layer, whose h_T
+  // every member masks and hands to the head itself)
+  ed.share0 = shared && c->ens_share && d.L > 1 ? 1 : 0;
+  const uint32_t thr_gcn = (uint32_t)std::lround((double)a.p_gcn * 16777216.0);
+  float* ringH = c->ens_ring.as<float>();
+  float* ringC = ringH + ring;
+  float* P = c->ens_pred.as<float>();
+  for (int e0 = 0; e0 < E; e0 += G) {
+    const int g = std::min(G, E - e0);
+    if (!shared) {
+      // STGCN features of member e0 + z under its own masks: conv k over the T N-row samples (the t = 0 rows
+      // with the graph), then the kind-1 mask of (step e, layer k) at the batch-wide element index
+      // ((done + b) T N + row) Hc + channel = base + the buffer's own linear index
+      const int rps = d.T * d.N;
+      const int32_t* ell_c = c->ell_c.as<int32_t>();
+      const float* ell_v = c->ell_v.as<float>();
+      float* bufs[2] = {cw.gcnA, cw.gcnB};
+      for (int z = 0; z < g; ++z) {
+        const float* src = nullptr;
+        for (int k = 0; k < 4; ++k) {
+          const bool last = k == 3;
+          float* dst = last ? cw.F + (int64_t)z * fslab : bufs[k & 1];
+          TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
+                launch_gcn_layer(s, d, k, B, B, k == 0 ? xt : nullptr, src, dst, last, true, c->gcn + c->go.w[k],
+                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N, nullptr));
+          if (!last)
+            TIMED(c, s, C_GCN, 0,
+                  launch_ens_dropout(s, dst, (int64_t)B * rps * d.Hc, 1, a.seed, 1, e0 + z, k, thr_gcn,
+                                     1.f / (1.f - a.p_gcn), (uint64_t)a.done * rps * d.Hc));
+          src = dst;
+        }
+      }
+    }
+    ed.e0 = e0;
+    for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+      FwdWave wv{};
+      double fl = 0.0;
+      fwd_wave(d, cw, c->po, diag, 0, false, wv);
+      for (int q = 0; q < wv.n; ++q) {  // layer 0 once when shared, without its projection when tabled
+        const double k1 = (wv.l[q] == 0 && have_xg ? 0 : wv.lo[q].cin) + (wv.t[q] > 0 ? d.H : 0);
+        fl += 2.0 * (wv.l[q] == 0 && ed.share0 ? 1 : g) * M * 4 * d.H * k1;
+      }
+      TIMED(c, s, C_FWD, fl,
+            launch_lstm_fwd_infer_drop(s, d, cw, diag, theta, c->po, ringH, ringC, g, shared ? 0 : fslab, ed));
+    }
+    // (the rings are laid out for g members: [L][2][g][M][H])
+    float* hT = ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * g * M * d.H;
+    if (ed.thr)
+      TIMED(c, s, C_HEAD, 0,
+            launch_ens_dropout(s, hT, (int64_t)M * d.H, g, a.seed, 3, e0, 0, ed.thr, ed.sc, (uint64_t)ed.row0 * d.H));
+    Work hw = cw;
+    hw.Z = g;
+    TIMED(c, s, C_HEAD, 2.0 * g * M * d.HfC * d.H,
+          launch_head_pred(s, d, hw, hT, (int64_t)M * d.H, theta, 0, c->po, P + (int64_t)e0 * M * d.HfC));
+  }
+  if (E > 32 && !c->ens_lds_set) {
+    const hipError_t st = ens_stats_prepare();
+    if (st != hipSuccess)
+      return fail(SMAML_EHIP, std::string("smaml_forecast_ensemble: raising k_ens_stats's dynamic LDS limit to 64 KB "
+                                          "(more than 32 members) failed: ") + hipGetErrorString(st));
+    c->ens_lds_set = true;
+  }
+  TIMED(c, s, C_MISC, 0,
+        launch_ens_stats(s, d, B, E, P, xt, scale_dev, mean, spread, member_pred, a.nwin * d.N * d.HfC,
+                         c->fc_part.as<float>(), scores, a.done == 0));
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
 bool graph_set(const smaml_ctx* c) { return c->ell_c.ptr && c->ell_v.ptr; }
 
 int require_ready(smaml_ctx* c) {
@@ -1727,7 +1885,79 @@ int smaml_forecast(smaml_ctx* c, void* stream, const float* theta, int32_t task,
 int64_t smaml_forecast_bytes(const smaml_ctx* c) {
   if (!c) return 0;
   return c->fc_ring.cap + c->fc_F.cap + c->fc_gcnA.cap + c->fc_gcnB.cap + c->fc_xg.cap + c->fc_pred.cap +
-         c->fc_part.cap + c->fc_scale.cap;
+         c->fc_part.cap + c->fc_scale.cap + c->ens_ring.cap + c->ens_pred.cap;
+}
+
+int smaml_forecast_ensemble(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
+                            int32_t nwin, int32_t batch, int32_t members, float p_gcn, float p_lstm, uint32_t seed,
+                            const float* scale_host, float* mean, float* spread, float* member_pred, double* scores) {
+  // (the checks that need no context first: they run without a device too)
+  if (!mean && !spread && !member_pred && !scores)
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: mean, spread, member_pred and scores are all NULL");
+  if (nwin <= 0 || batch <= 0 || !windows_host)
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: nwin and batch must be positive");
+  if (members < 1 || members > 64)
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: members must be in 1..64, got " + std::to_string(members));
+  if (!(p_gcn >= 0.f && p_gcn < 1.f) || !(p_lstm >= 0.f && p_lstm < 1.f))
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: dropout probabilities must be in [0, 1)");
+  TRY(require_ready(c));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !aligned16(theta))
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: theta must be a 16-byte aligned device pointer");
+  if (task < 0 || task >= (int)c->feats.size())
+    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: task out of range");
+  const Dims& d = c->d;
+  const int B0 = std::min(batch, nwin);
+  if ((int64_t)d.T * B0 * d.N * 4 * d.H >= (1ll << 31))
+    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^31");
+  const int tt = c->t_total[task];
+  std::vector<const float*> ptrs(nwin);
+  for (int i = 0; i < nwin; ++i) {
+    const int wv = windows_host[i];
+    if (wv < 0 || wv + d.T > tt || (scores && wv + d.T + d.Hf >= tt))
+      return fail(SMAML_EINVAL, "smaml_forecast_ensemble: window " + std::to_string(i) + " (start " +
+                                    std::to_string(wv) +
+                                    (scores && wv >= 0 && wv + d.T <= tt ? ") has no targets in" : ") does not fit") +
+                                    " the stream of " + std::to_string(tt) + " steps");
+    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
+  }
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  hipStream_t s = (hipStream_t)stream;
+  // as smaml_forecast: the workspace view of the training state is put back
+  const Work saved = c->w;
+  const int act = c->act_B;
+  auto run = [&]() -> int {
+    const float* scale_dev = nullptr;
+    if (scores && scale_host) {
+      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
+      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
+      scale_dev = c->fc_scale.as<float>();
+    }
+    TRY(upload_xtab(c, s, ptrs.data(), nwin));
+    EnsArgs a{};
+    a.E = members;
+    a.p_gcn = p_gcn;
+    a.p_lstm = p_lstm;
+    a.seed = seed;
+    a.nwin = nwin;
+    for (int64_t done = 0; done < nwin; done += batch) {
+      const int B = (int)std::min<int64_t>(batch, nwin - done);
+      bool consec = B > 1;
+      for (int b = 1; b < B && consec; ++b) consec = windows_host[done + b] == windows_host[done] + b;
+      const float* const* xt = nullptr;
+      TRY(xtab_at(c, done, &xt));
+      a.done = done;
+      const int64_t off = done * d.N * d.HfC;
+      TRY(ensemble_pass(c, s, theta, xt, B, consec, a, scale_dev, mean ? mean + off : nullptr,
+                        spread ? spread + off : nullptr, member_pred ? member_pred + off : nullptr, scores));
+    }
+    return SMAML_OK;
+  };
+  const int rc = run();
+  c->w = saved;
+  c->act_B = act;
+  return rc;
 }
 
 int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,
@@ -2271,6 +2501,10 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->ad_phase_sync = (int)value;
   } else if (k == "adapt_group" && value >= -1 && value <= ADAPT_MAX_GROUP) {
     c->ad_group = (int)value;
+  } else if (k == "ens_share" && (value == 0 || value == 1)) {
+    c->ens_share = (int)value;
+  } else if (k == "ens_group" && value >= -1 && value <= 64) {
+    c->ens_group = (int)value;
   } else if (k == "adapt_gcn_batch" && value >= 0 && value <= 256) {
     c->ad_gcn_batch = (int)value;
   } else if (k == "wgrad_group_wgs" && value >= 1) {

@@ -102,6 +102,7 @@ enum Variant {
   V_WGRAD_DEDUP,     // layer 0's input-weight gradient over distinct stream rows (k_dg_rowsum + gathered k_wgrad)
   V_F_COMPACT,       // GCN features stored once per distinct stream row (Work::fcompact)
   V_FWD_INFER,       // k_lstm_fwd_infer (smaml_forecast: only h and c kept, in a two-slot ring)
+  V_FWD_INFER_DROP,  // k_lstm_fwd_infer_drop (smaml_forecast_ensemble: the same step, grid z = ensemble member)
   NVAR
 };
 
@@ -451,6 +452,32 @@ inline int64_t infer_ring_floats(const Dims& d, int Z, int M) { return (int64_t)
 inline const float* infer_ring_hT(const Dims& d, const float* ringH, int Z, int M) {
   return ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * Z * M * d.H;
 }
+// ---- ensemble forecast (smaml_forecast_ensemble; kernels.hip) ----
+// Mask state of one launch of k_lstm_fwd_infer_drop: member e = e0 + z uses the sites (seed, kind, step e,
+// layer) with task id 0; element indices are those of one training batch holding the call's whole window
+// list (Mtot = nwin N rows per step), of which this pass holds rows [row0, row0 + M).
+struct EnsDrop {
+  uint32_t seed = 0;
+  uint32_t thr = 0;  // round(p_lstm * 2^24); 0 = off
+  float sc = 1.f;    // 1 / (1 - p_lstm)
+  int e0 = 0;        // member of z = 0
+  int64_t row0 = 0, Mtot = 0;
+  int share0 = 0;    // layer 0 computed by z = 0 only and read by every member (no mask below its output)
+};
+// G members' diagonal on rings [L][2][G][M][H]; member z's features fz floats past w.F (0: shared, then the
+// XG table of w.xgd applies)
+void launch_lstm_fwd_infer_drop(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
+                                const ParamOff& po, float* ringH, float* ringC, int G, int64_t fz, const EnsDrop& ed);
+// x[z][i] = drop(x[z][i]), z < G, i < n, site (seed, kind, step0 + z, layer), element base + i
+void launch_ens_dropout(hipStream_t s, float* x, int64_t n, int G, uint32_t seed, int kind, int step0, int layer,
+                        uint32_t thr, float sc, uint64_t base);
+// Mean, spread, member copies and the four sums of one pass from its member predictions P [E][B][N*Hf][C]
+// (k_ens_stats): part [skill_blocks][HfC][4] f32 partials, added in double onto scores [4][Hf][C] (first:
+// overwritten). Any of mean / spread / member_pred / scores may be null.
+hipError_t ens_stats_prepare();  // raise k_ens_stats's dynamic-LDS limit on the current device (needed above E = 32)
+void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P, const float* const* xtab,
+                      const float* scale, float* mean, float* spread, float* member_pred, int64_t mstride, float* part,
+                      double* scores, bool first);
 // launch_head_loss's prediction alone from given h_T rows (hz floats between tasks) into pred [Z][M][HfC]
 void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
                       int64_t tstride, const ParamOff& po, float* pred);

@@ -584,6 +584,66 @@ __global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_infer
                            xgt);
 }
 
+// ---- MC-dropout form of the inference step (smaml_forecast_ensemble) ---------------------------------
+// k_lstm_fwd_infer with the grid's z axis as the ensemble-member axis: member e = ed.e0 + z runs the same
+// tile, main loop, ring scheme and weight images under its own masks (site (seed, kind 2, step e, layer
+// l - 1) on the A operand h(l-1, t) of layers >= 1, element ((t Mtot) + row0 + m) H + unit: the indices of
+// one training batch holding the call's whole window list). theta, the weight images and the XG table are
+// shared by all members; F is per member fz floats apart (0: shared). Rings [L][2][Z][M][H] as
+// k_lstm_fwd_infer's. ed.share0: nothing is masked below layer 0's output, so layer 0 is the same in every
+// member: only z = 0 computes it (the other members' layer-0 blocks leave at once) and every member's
+// layer 1 reads slot z = 0 of layer 0's ring. The ring argument of k_lstm_fwd_infer holds unchanged: the
+// shared slots are written and read on the same diagonals as a member's own would be.
+// The mask is applied to the fetched tile registers before they are staged, so unlike k_lstm_fwd_step_drop
+// nothing of it lives across the main loop: the eval step's register budget (4 waves/SIMD, no spill).
+template <int H, bool IMG>
+__global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_infer_drop(
+    const float* __restrict__ F, int64_t fz, float* __restrict__ ringH, float* __restrict__ ringC,
+    const float* __restrict__ th, FwdWave wv, int T, int M, GateImgs gi, XgDedup xd, EnsDrop ed) {
+  __shared__ float smem[CfgGate::SMEM_FLOATS];
+  int l, t, b0;
+  LayerOff lo;
+  const Blk bk = xcd_block();
+  wave_problem(wv, bk.x, l, t, lo, b0);
+  const int z = bk.z, Z = (int)gridDim.z;
+  if (ed.share0 && l == 0 && z > 0) return;
+  const int64_t slot = (int64_t)M * H;
+  auto at = [&](float* ring, int ll, int tt) {
+    const int zz = ed.share0 && ll == 0 ? 0 : z;
+    return ring + ((int64_t)(2 * ll + (tt & 1)) * Z + zz) * slot;
+  };
+  const int cin = lo.cin;
+  const float* Hp = t > 0 ? at(ringH, l, t - 1) : nullptr;
+  int tm, ug;
+  constexpr int UPB = CfgGate::WAVES_N;
+  if (!gate_tile(bk.x - b0, (M + CfgGate::BM - 1) / CfgGate::BM, (H + 32 * UPB - 1) / (32 * UPB), tm, ug)) return;
+  const int m0 = tm * CfgGate::BM, n0 = ug * CfgGate::BN;
+  Acc<CfgGate> acc;
+  acc.zero();
+  const float* xgt = xd.xg && l == 0 ? xd.xg + xg_dedup_row0(t, M, xd.N) * (4 * H) : nullptr;
+  const int kbeg = xgt ? cin : 0;
+  const float* X = l > 0 ? at(ringH, l - 1, t) : xgt ? F : F + (int64_t)z * fz + (int64_t)t * M * cin;
+  const XDrop xdm{drop_site(ed.seed, 2, ed.e0 + z, l > 0 ? l - 1 : 0), ed.thr, ed.sc,
+                  ((uint64_t)t * (uint64_t)ed.Mtot + (uint64_t)ed.row0) * H, H};
+  const SegKCtDrop la{{X, Hp}, {cin, H}, M, xdm, l > 0 && ed.thr != 0 ? 1 : 0};
+  if constexpr (IMG) {
+    int64_t o0 = 0, o1 = 0;
+#pragma unroll
+    for (int q = 0; q < MAX_LAYERS; ++q)
+      if (q == l) {
+        o0 = gi.off[q][0];
+        o1 = gi.off[q][1];
+      }
+    const SegGateImg<2> lbi{{gi.th + o0, gi.th + o1}, {cin, H}};
+    gemm_mainloop<CfgGate>(la, lbi, m0, n0, kbeg, cin + (t > 0 ? H : 0), acc, smem);
+  } else {
+    const SegGateBt<2> lbt{{th + lo.wih, th + lo.whh}, {cin, H}, H};
+    gemm_mainloop<CfgGate>(la, lbt, m0, n0, kbeg, cin + (t > 0 ? H : 0), acc, smem);
+  }
+  infer_cell_t<H, CfgGate>(acc, th, lo, at(ringC, l, t - 1), at(ringC, l, t), at(ringH, l, t), m0, ug, t > 0, M, smem,
+                           xgt);
+}
+
 // Layer 0's input projection of a step whose every task reads B consecutive windows, once per distinct
 // stream row (kernels.h XgDedup): out[z][r][g H + j] = F_row(r) . W_ih0[g H + j] with the gate GEMM's own
 // tile (CfgGate), column mapping, K order and weight images. The tangent gate kernel starts its
@@ -984,6 +1044,45 @@ void launch_lstm_fwd_infer(hipStream_t s, const Dims& d, const Work& w, int diag
   }
 }
 
+// Diagonal `diag` of the ensemble's inference forward for G members (k_lstm_fwd_infer_drop; grid z = member).
+// w is the pass's single-task view (Z = 1: F, gimg, xgd of theta); F of member z is fz floats past w.F.
+void launch_lstm_fwd_infer_drop(hipStream_t s, const Dims& d, const Work& w, int diag, const float* theta,
+                                const ParamOff& po, float* ringH, float* ringC, int G, int64_t fz, const EnsDrop& ed) {
+  const int ntm = (w.M + CfgGate::BM - 1) / CfgGate::BM;
+  const int ngrp = (d.H + 32 * CfgGate::WAVES_N - 1) / (32 * CfgGate::WAVES_N);
+  FwdWave wv{};
+  fwd_wave(d, w, po, diag, gate_blocks(ntm, ngrp), false, wv);
+  if (wv.n == 0) return;
+  dim3 grid(wv.off[wv.n], 1, G);
+  count_variant(w, V_FWD_INFER_DROP);
+  XgDedup xd = w.xgd;
+  if (xd.src != theta || fz != 0) xd.xg = nullptr;  // (the table is of the shared features only)
+  if (w.gimg.th && w.gimg_src == theta) {
+    SMAML_DISPATCH_H(d.H, (k_lstm_fwd_infer_drop<HT, true><<<grid, CfgGate::NTH, 0, s>>>(w.F, fz, ringH, ringC, theta, wv,
+                                                                                         d.T, w.M, w.gimg, xd, ed)));
+  } else {
+    SMAML_DISPATCH_H(d.H, (k_lstm_fwd_infer_drop<HT, false><<<grid, CfgGate::NTH, 0, s>>>(w.F, fz, ringH, ringC, theta,
+                                                                                          wv, d.T, w.M, w.gimg, xd, ed)));
+  }
+}
+
+// x[z][i] = drop(x[z][i]) in place, i < n, with the masks of site (seed, kind, step0 + z, layer) at element
+// base + i: the ensemble's head-input mask (kind 3, x = the top layer's h_T rows [G][M][H], base = row0 H)
+// and its per-member GCN-output masks (kind 1, one member per launch, base = first sample x T N Hc).
+__global__ void k_ens_dropout(float* __restrict__ x, int64_t n, uint32_t seed, int kind, int step0, int layer,
+                              uint32_t thr, float sc, uint64_t base) {
+  const uint32_t site = drop_site(seed, kind, step0 + (int)blockIdx.y, layer);
+  float* xz = x + (int64_t)blockIdx.y * n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    xz[i] = drop_keep(site, base + (uint64_t)i, thr) ? xz[i] * sc : 0.f;
+}
+
+void launch_ens_dropout(hipStream_t s, float* x, int64_t n, int G, uint32_t seed, int kind, int step0, int layer,
+                        uint32_t thr, float sc, uint64_t base) {
+  int nb = (int)std::min<int64_t>((n + NT - 1) / NT, 4096);
+  k_ens_dropout<<<dim3(nb, G), NT, 0, s>>>(x, n, seed, kind, step0, layer, thr, sc, base);
+}
+
 // ---- pre-split gate-GEMM weight images --------------------------------------------------
 int64_t gate_img_bytes(const Dims& d, GateImgs* gi) {
   const int nug = (d.H + 31) / 32;
@@ -1378,6 +1477,109 @@ void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, c
   const int nblk = skill_blocks(d, B);
   k_skill_part<<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part);
   k_skill_final<<<(3 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, skill, first ? 1 : 0);
+}
+
+// ---- ensemble statistics (smaml_forecast_ensemble) --------------------------------------------------
+// From the pass's member predictions P [E][B][N*Hf][C]: per element the ensemble mean (member sum in member
+// order / E) and the unbiased standard deviation about it (two-pass; 0 at E = 1; both in double, rounded
+// once), optionally a copy of every
+// member into member_pred (member stride mstride), and with `part` the pass's four probabilistic sums per
+// target lead h' and variable c with k_skill_part's blocks, pairing and scale:
+//   [0] sum (s (mu - y))^2, [1] sum s^2 var, [2] sum s CRPS, [3] sum (s (y_last - y))^2,
+//   CRPS = (1/E) sum_i |x_i - y| - (1/E^2) sum_{i<j} |x_i - x_j|   (the pairs (i, j) in lexicographic order).
+// A thread parks its element's E members in a column of LDS (xs[e][thread]: no per-thread array) and forms
+// everything from there. f32 per block (each thread its pairs in order, then block_sum's fixed tree);
+// k_ens_final adds the blocks in order in double onto scores [4][Hf][C]. No atomics: bitwise repeatable.
+__global__ __launch_bounds__(NT) void k_ens_stats(const float* __restrict__ P, int E, const float* const* __restrict__ xtab,
+                                                  const float* __restrict__ scale, int B, int N, int Hf, int C, int T,
+                                                  int yld, float* __restrict__ mean, float* __restrict__ spread,
+                                                  float* __restrict__ member_pred, int64_t mstride,
+                                                  float* __restrict__ part) {
+  extern __shared__ float xs[];  // [E][NT]
+  __shared__ float red[NT / 64];
+  const int hc = blockIdx.x, hp = hc / C, c = hc - hp * C;
+  const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, B * N);
+  const float sc = scale ? scale[c] : 1.f;
+  const int64_t estride = (int64_t)B * N * Hf * C;
+  const float invE = 1.f / (float)E;
+  float se = 0.f, sv = 0.f, sr = 0.f, pe = 0.f;
+  float* col = xs + threadIdx.x;
+  for (int p = p0 + (int)threadIdx.x; p < p1; p += NT) {
+    const int sm = p / N, n = p - sm * N;
+    const int64_t idx = ((int64_t)sm * N * Hf + (int64_t)hp * N + n) * C + c;
+    // (mean and variance accumulate in double and are rounded once: a mean that cancels among the members
+    // keeps its relative accuracy)
+    double sum = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const float x = P[(int64_t)e * estride + idx];
+      col[e * NT] = x;
+      sum += (double)x;
+      if (member_pred) member_pred[(int64_t)e * mstride + idx] = x;
+    }
+    const double mud = sum / (double)E;
+    const float mu = (float)mud;
+    double ss = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const double dv = (double)col[e * NT] - mud;
+      ss = fma(dv, dv, ss);
+    }
+    const float var = E > 1 ? (float)(ss / (double)(E - 1)) : 0.f;
+    if (mean) mean[idx] = mu;
+    if (spread) spread[idx] = sqrtf(var);
+    if (part) {
+      const float* xw = xtab[sm];
+      const float y = xw[((int64_t)(T + 1 + hp) * N + n) * yld + c];
+      const float yl = xw[((int64_t)(T - 1) * N + n) * yld + c];
+      float ae = 0.f, pw = 0.f;
+      for (int i = 0; i < E; ++i) {
+        const float xi = col[i * NT];
+        ae += fabsf(xi - y);
+        for (int j = i + 1; j < E; ++j) pw += fabsf(xi - col[j * NT]);
+      }
+      const float crps = ae * invE - pw * invE * invE;
+      const float em = sc * (mu - y), q = sc * (yl - y);
+      se = fmaf(em, em, se);
+      sv = fmaf(sc * sc, var, sv);
+      sr = fmaf(sc, crps, sr);
+      pe = fmaf(q, q, pe);
+    }
+  }
+  if (!part) return;
+  float* o = part + ((int64_t)blockIdx.y * gridDim.x + hc) * 4;
+  const float s0 = block_sum(se, red);
+  const float s1 = block_sum(sv, red);
+  const float s2 = block_sum(sr, red);
+  const float s3 = block_sum(pe, red);
+  if (threadIdx.x == 0) {
+    o[0] = s0;
+    o[1] = s1;
+    o[2] = s2;
+    o[3] = s3;
+  }
+}
+
+__global__ void k_ens_final(const float* __restrict__ part, int nblk, int HfC, double* __restrict__ scores, int first) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 4 * HfC) return;
+  const int k = i / HfC, hc = i - k * HfC;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += (double)part[((int64_t)b * HfC + hc) * 4 + k];
+  scores[i] = first ? s : scores[i] + s;
+}
+
+// E = 64 columns are 64 KB of dynamic LDS beside k_ens_stats's static words: above the default per-kernel
+// limit, so the limit is raised on the current device (the caller does it once per context and checks it).
+hipError_t ens_stats_prepare() {
+  return hipFuncSetAttribute((const void*)k_ens_stats, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+}
+
+void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P, const float* const* xtab,
+                      const float* scale, float* mean, float* spread, float* member_pred, int64_t mstride, float* part,
+                      double* scores, bool first) {
+  const int nblk = skill_blocks(d, B);
+  k_ens_stats<<<dim3(d.HfC, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+      P, E, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, mean, spread, member_pred, mstride, scores ? part : nullptr);
+  if (scores) k_ens_final<<<(4 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, scores, first ? 1 : 0);
 }
 
 // ====================================================================================

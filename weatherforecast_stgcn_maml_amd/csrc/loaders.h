@@ -430,6 +430,34 @@ struct SegKCDrop {
   }
 };
 
+// SegKCt<2> whose segment 0 (x = h(l-1, t)) is dropout-masked as it is fetched (XDrop, kind 2): the tile
+// loader's counterpart of LstmFwdA<H, true>. Rows past the edge are clamped like SegKCt's (masked with the
+// clamped row's index: never stored).
+struct SegKCtDrop {
+  static constexpr bool kTileFetch = true;
+  const float* p[2];
+  int w[2];
+  int rows;
+  XDrop d;
+  int on;  // mask segment 0 (layers >= 1 with LSTM dropout)
+  template <int ROWS, int F4, int NTH, bool KC, int BK>
+  __device__ __forceinline__ void fetch(int row0, int k0, float4 (&r)[F4]) const {
+    static_assert(KC, "SegKCtDrop is a k-contiguous operand");
+    const float* b;
+    int ws, kk;
+    seg_pick<2>(p, w, k0, b, ws, kk);
+    const bool mask = on && k0 < w[0];  // uniform: a K-tile lies inside one segment
+    b += kk + (int64_t)row0 * ws;
+#pragma unroll
+    for (int i = 0; i < F4; ++i) {
+      const int f = (int)threadIdx.x + NTH * i;
+      const int dr = min(row0 + f / (BK / 4), rows - 1) - row0;
+      r[i] = ldo(b, 4u * (uint32_t)(dr * ws + 4 * (f % (BK / 4))));
+      if (mask) r[i] = d.apply(r[i], row0 + dr, kk + 4 * (f % (BK / 4)));
+    }
+  }
+};
+
 // Gate nonlinearities. SMAML_FAST_GATES (default) uses the hardware transcendentals:
 // v_exp_f32 on x*log2(e) and v_rcp_f32 (1 ulp), and for tanh 1 - 2/(1+e^{2|x|}) with an odd
 // Taylor polynomial below |x| < 0.125 (no cancellation near 0). Relative error <~1e-6 per
