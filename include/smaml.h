@@ -38,16 +38,27 @@ extern "C" {
 
 typedef struct smaml_ctx smaml_ctx;
 
-/* Model shapes: model.STGCN(...) (model.py:8-28) + HybridSTGCN_LSTM(...) (hybrid_model.py:16-58). */
+/* Model shapes: model.STGCN(...) (model.py:8-28) + HybridSTGCN_LSTM(...) (hybrid_model.py:16-58).
+ *
+ * Two sets of rules. smaml_create / smaml_param_layout accept what the GCN entry points
+ * (smaml_gcn_conv*, smaml_gcn_forward, smaml_relu_mask, smaml_dropout) can run: every dimension positive,
+ * input_channels and hidden_channels multiples of 4, lstm_hidden_size 32 / 64 / 128 / 256,
+ * lstm_num_layers <= 8, forecast_horizon * output_channels <= 128, output_channels <= input_channels.
+ * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_lstm_forward,
+ * smaml_lstm_backward, smaml_head_loss, smaml_meta_step, smaml_inner_loop, smaml_adapt_prepare[_multi],
+ * smaml_adapt_steps[_multi], smaml_forecast, smaml_forecast_ensemble) requires in addition
+ *   hidden_channels % 16 == 0                        (the layer-0 K segment of the gate-GEMM tile loaders)
+ *   (forecast_horizon * output_channels) % 4 == 0    (16-byte reads of prediction rows)
+ * and returns SMAML_EINVAL naming the dimension otherwise, before it allocates or launches anything. */
 typedef struct smaml_dims {
   int32_t num_nodes;         /* N: grid nodes per region (441 = 21x21) */
-  int32_t window_size;       /* T (24) */
-  int32_t input_channels;    /* 24 */
-  int32_t hidden_channels;   /* GCN hidden (256) */
-  int32_t lstm_hidden_size;  /* 128 (multiple of 32) */
-  int32_t lstm_num_layers;   /* 4 */
+  int32_t window_size;       /* T (24); any positive length */
+  int32_t input_channels;    /* 24 (multiple of 4) */
+  int32_t hidden_channels;   /* GCN hidden (256): multiple of 4; of 16 for the LSTM / head entry points */
+  int32_t lstm_hidden_size;  /* 128 (32, 64, 128 or 256) */
+  int32_t lstm_num_layers;   /* 4 (1 .. 8) */
   int32_t forecast_horizon;  /* 8 */
-  int32_t output_channels;   /* 12 */
+  int32_t output_channels;   /* 12 (Hf*C <= 128; a multiple of 4 for the LSTM / head entry points) */
 } smaml_dims;
 
 const char* smaml_last_error(void);

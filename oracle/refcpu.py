@@ -234,7 +234,8 @@ class TaskData:
     def xy(self, i: int):
         W, Hf, N = self.dims.window_size, self.dims.forecast_horizon, self.dims.num_nodes
         x = self.features[i:i + W].reshape(W * N, -1)
-        y = self.features[i + W + 1:i + W + 1 + Hf, :, :12].reshape(Hf * N, 12)
+        C = self.dims.output_channels
+        y = self.features[i + W + 1:i + W + 1 + Hf, :, :C].reshape(Hf * N, C)
         return x, y
 
     def gcn(self, i: int, P):
@@ -402,8 +403,8 @@ def regional_eval(P: Dict[str, torch.Tensor], features: np.ndarray, edge_index, 
         with torch.no_grad():
             preds.append(hybrid_forward(P, x, ei, d).numpy())
         trues.append(y.numpy())
-    y_pred = np.mean(preds, axis=0).reshape(Hf, N, 12).mean(axis=1)
-    y_true = np.mean(trues, axis=0).reshape(Hf, N, 12).mean(axis=1)
+    y_pred = np.mean(preds, axis=0).reshape(Hf, N, d.output_channels).mean(axis=1)
+    y_true = np.mean(trues, axis=0).reshape(Hf, N, d.output_channels).mean(axis=1)
     mean, std = np.array(stats["mean"]), np.array(stats["std"])
     names = ["u10", "v10", "t2m", "d2m", "sp", "tp"]
     res, tot, cnt = {}, 0.0, 0

@@ -1,5 +1,6 @@
-"""Per-kernel VGPR / AGPR / scratch / occupancy of the library sources (gfx950), H=128 instances.
-Usage: python tools/res_usage.py [-DSMAML_X=1 ...]"""
+"""Per-kernel VGPR / AGPR / scratch / occupancy of the library sources (gfx950), the instances of one
+LSTM hidden size (RES_H = 32, 64, 128 or 256; default 128) and the kernels without that parameter.
+Usage: [RES_H=256] python tools/res_usage.py [-DSMAML_X=1 ...]"""
 import os
 import re
 import subprocess
@@ -7,7 +8,9 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(REPO, "weatherforecast_stgcn_maml_amd", "csrc")
-for f in ("kernels", "kernels_dual"):
+RES_H = os.environ.get("RES_H", "128")
+OTHER_H = "|".join(h for h in ("32", "64", "128", "256") if h != RES_H)
+for f in ("kernels", "kernels_dual", "kernels_small"):
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(REPO, "include"),
                         "-I", CS, *sys.argv[1:], "-c", os.path.join(CS, f + ".hip"), "-o", f"/tmp/res_{f}.o",
                         "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
@@ -26,7 +29,7 @@ for f in ("kernels", "kernels_dual"):
             cur[k.strip()] = v.strip()
     for c in rows:
         n = c["name"]
-        if re.search(r"^_ZN5smaml\d+k_[a-z_]+ILi(32|64|256)E", n):
+        if re.search(r"^_ZN5smaml\d+k_[a-z_]+ILi(%s)E" % OTHER_H, n):
             continue
         short = re.sub(r"^_ZN5smaml\d+", "", n)[:int(os.environ.get("RES_W", "48"))]
         print(f"{short:48s} vgpr {c.get('VGPRs', '?'):>4s} agpr {c.get('AGPRs', '?'):>4s} "

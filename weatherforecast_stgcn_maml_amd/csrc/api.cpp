@@ -70,6 +70,28 @@ int check_dims(const smaml_dims* d) {
   return SMAML_OK;
 }
 
+// What the LSTM gate-GEMM, BPTT and head launches need beyond check_dims (a context that only runs the GCN
+// entry points, e.g. the GCNConv drop-in's hidden_channels = 4, needs none of it). Called by every entry
+// point that plans such a launch, before it allocates or launches anything.
+//  - hidden_channels % 16: the tile loaders of the default path (loaders.h "tile loaders": SegKCt,
+//    SegGateBt, SegGateImg, k_xg_dedup, the batch-1 k_gemm_nt, the 4-segment tangent loaders) pick a
+//    segment once per BK = 16 wide K tile, and the gate images hold w / 16 tiles per segment: a layer-0
+//    input segment that is no multiple of 16 would read across row ends and past the operand.
+//  - forecast_horizon*output_channels % 4: dpred / pred rows are read 16 bytes at a time (k_gemm_nn's
+//    RowMajorKC, the head weight gradients); a row that is no multiple of 4 floats misaligns every other
+//    row and the K tail reads past the row (at the last row, past the buffer).
+int check_lstm_dims(const smaml_dims& d, const char* who) {
+  if (d.hidden_channels % 16)
+    return fail(SMAML_EINVAL, std::string(who) + ": hidden_channels must be a multiple of 16 for the LSTM and head "
+                                  "entry points (the layer-0 K segment of the gate GEMM tiles), got " +
+                                  std::to_string(d.hidden_channels));
+  if ((d.forecast_horizon * d.output_channels) % 4)
+    return fail(SMAML_EINVAL, std::string(who) + ": forecast_horizon*output_channels must be a multiple of 4 for "
+                                  "the LSTM and head entry points (16-byte reads of prediction rows), got " +
+                                  std::to_string(d.forecast_horizon * d.output_channels));
+  return SMAML_OK;
+}
+
 void layout(const smaml_dims& d, int which, std::vector<Spec>& specs, int64_t& total) {
   specs.clear();
   int64_t off = 0;
@@ -734,6 +756,11 @@ bool f_compact_ok(smaml_ctx* c, bool consec) {
   const Dims& d = c->d;
   const Work& w = c->w;
   const Knobs& kn = c->kn;
+  // The compact rows of a task, (2B + T - 2) N, live in its [T][B N] slab of F (and of a kept so_F slot):
+  // they fit iff (T - 2)(B - 1) >= 0. A window of ONE step shares no stream row with its neighbours, its
+  // (2B - 1) N compact rows would run (B - 1) N rows past the slab -- into the next task's rows and, for the
+  // last task, past the buffer.
+  if (d.T < 2) return false;
   if (!consec || !kn.f_compact || !kn.gcn_dedup || !kn.xg_dedup || !kn.wgrad_dedup || w.B <= 1 || w.drop.gcn() ||
       w.drop.lstm() || (int64_t)w.Z * w.M <= kn.wgrad_group_max_rows)
     return false;
@@ -1779,6 +1806,7 @@ int smaml_relu_mask(smaml_ctx* c, void* stream, float* g, const float* h, int64_
 int smaml_forward(smaml_ctx* c, void* stream, const float* theta, const float* const* x_host, int32_t nsamples,
                   float* pred, float* feats) {
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_forward"));
   if (!theta || !x_host || nsamples <= 0 || !pred) return fail(SMAML_EINVAL, "bad forward arguments");
   for (int i = 0; i < nsamples; ++i)
     if (!x_host[i] || !aligned16(x_host[i])) return fail(SMAML_EINVAL, "sample x pointers must be 16-B aligned");
@@ -1831,6 +1859,7 @@ int smaml_forecast(smaml_ctx* c, void* stream, const float* theta, int32_t task,
   if (nwin <= 0 || batch <= 0 || !windows_host)
     return fail(SMAML_EINVAL, "smaml_forecast: nwin and batch must be positive");
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_forecast"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (!theta || !aligned16(theta))
     return fail(SMAML_EINVAL, "smaml_forecast: theta must be a 16-byte aligned device pointer");
@@ -1901,6 +1930,7 @@ int smaml_forecast_ensemble(smaml_ctx* c, void* stream, const float* theta, int3
   if (!(p_gcn >= 0.f && p_gcn < 1.f) || !(p_lstm >= 0.f && p_lstm < 1.f))
     return fail(SMAML_EINVAL, "smaml_forecast_ensemble: dropout probabilities must be in [0, 1)");
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_forecast_ensemble"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (!theta || !aligned16(theta))
     return fail(SMAML_EINVAL, "smaml_forecast_ensemble: theta must be a 16-byte aligned device pointer");
@@ -1964,6 +1994,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
                     const int32_t* windows_host, float inner_lr, float max_norm, float query_scale,
                     float* meta_grad, float* losses, float* norms, float* fast_out) {
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_meta_step"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (!theta || steps < 0 || batch <= 0 || !windows_host) return fail(SMAML_EINVAL, "bad meta_step arguments");
   if (order < 0 || order > 2) return fail(SMAML_EINVAL, "order must be 0, 1 or 2");
@@ -2222,6 +2253,7 @@ static int ad_check_tasks(const smaml_ctx* c, const char* who, int32_t nregions,
 
 int smaml_adapt_prepare(smaml_ctx* c, void* stream, int32_t batch) {
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_prepare"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (batch <= 0) return fail(SMAML_EINVAL, "bad adapt_prepare batch");
   TRY(ensure_device(c));
@@ -2236,6 +2268,7 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
                       float eps, float weight_decay, float max_norm, float* losses) {
   using clk = std::chrono::steady_clock;
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_steps"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (!theta || !m || !v || nsteps <= 0 || batch <= 0 || !windows_host || !lr_dev || !losses || step0 < 0)
     return fail(SMAML_EINVAL, "bad adapt_steps arguments");
@@ -2304,6 +2337,7 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
 
 int smaml_adapt_prepare_multi(smaml_ctx* c, void* stream, int32_t nregions, const int32_t* tasks_host, int32_t batch) {
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_prepare_multi"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (batch <= 0) return fail(SMAML_EINVAL, "bad adapt_prepare_multi batch");
   TRY(ad_check_tasks(c, "adapt_prepare_multi", nregions, tasks_host));
@@ -2325,6 +2359,7 @@ int smaml_adapt_steps_multi(smaml_ctx* c, void* stream, int32_t nregions, const 
                             float beta1, float beta2, float eps, float max_norm, float* losses) {
   using clk = std::chrono::steady_clock;
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_steps_multi"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
   if (!theta || !m || !v || nsteps <= 0 || batch <= 0 || !windows_host || !lr_dev || !weight_decay_host || !losses ||
       step0 < 0)
@@ -2547,6 +2582,7 @@ int smaml_adamw_step(smaml_ctx* c, void* stream, float* theta, const float* grad
 
 int smaml_backward(smaml_ctx* c, void* stream, const float* theta, const float* dpred, float* grad) {
   TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_backward"));
   if (!theta || !dpred || !grad) return fail(SMAML_EINVAL, "bad backward arguments");
   if (c->act_B < 1 || c->w.Z != 1) return fail(SMAML_ESTATE, "smaml_backward needs the activations of smaml_forward");
   TRY(ensure_device(c));
@@ -2594,6 +2630,7 @@ int smaml_gcn_forward(smaml_ctx* c, void* stream, const float* const* x_host, in
 int smaml_lstm_forward(smaml_ctx* c, void* stream, const float* theta, const float* feats, int32_t nsamples,
                        float* hT) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  TRY(check_lstm_dims(c->dims, "smaml_lstm_forward"));
   if (!theta || !feats || nsamples <= 0 || !hT) return fail(SMAML_EINVAL, "bad lstm_forward arguments");
   TRY(ensure_device(c));
   hipStream_t s = (hipStream_t)stream;
@@ -2615,6 +2652,7 @@ int smaml_lstm_forward(smaml_ctx* c, void* stream, const float* theta, const flo
 
 int smaml_lstm_backward(smaml_ctx* c, void* stream, const float* theta, const float* dhT, float* grad) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  TRY(check_lstm_dims(c->dims, "smaml_lstm_backward"));
   if (!theta || !dhT || !grad) return fail(SMAML_EINVAL, "bad lstm_backward arguments");
   if (c->act_B < 1 || c->w.Z != 1)
     return fail(SMAML_ESTATE, "smaml_lstm_backward needs the activations of smaml_lstm_forward");
@@ -2631,6 +2669,7 @@ int smaml_lstm_backward(smaml_ctx* c, void* stream, const float* theta, const fl
 int smaml_head_loss(smaml_ctx* c, void* stream, const float* theta, const float* hT, const float* const* y_host,
                     int32_t nsamples, float* pred, float* loss, float* dpred) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  TRY(check_lstm_dims(c->dims, "smaml_head_loss"));
   if (!theta || !hT || nsamples <= 0 || !pred) return fail(SMAML_EINVAL, "bad head_loss arguments");
   if (y_host && (!loss || !dpred)) return fail(SMAML_EINVAL, "loss and dpred are required with targets");
   if (!aligned16(hT) || !aligned16(theta)) return fail(SMAML_EINVAL, "hT / theta must be 16-byte aligned");

@@ -265,6 +265,7 @@ void launch_gcn_expand(hipStream_t s, const Dims& d, int Z, int B, const float* 
     k_gcn_compact<<<dim3(gx, (unsigned)Z), 256, 0, s>>>(C, F, B, d.T, blk);
     return;
   }
+  if (d.T < 2) return;  // one-step windows: no rows t >= 1 to expand (a grid of B (T - 1) = 0 blocks is no launch)
   const unsigned gx = (unsigned)std::min<int64_t>((blk / 4 + 255) / 256, 64);
   k_gcn_expand<<<dim3(gx, (unsigned)(Z * B * (d.T - 1))), 256, 0, s>>>(C, F, B, d.T, blk);
 }

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .config import ModelDims, WINDOW_SIZE, FORECAST_HORIZON
+from .config import ModelDims, WINDOW_SIZE, FORECAST_HORIZON, OUTPUT_CHANNELS
 
 
 def region_grid(lat_max: float = 23.0, lon_min: float = 75.0, n_lat: int = 21, n_lon: int = 21,
@@ -65,13 +65,14 @@ def t_total_for(samples: int, window: int = WINDOW_SIZE, horizon: int = FORECAST
 
 
 def sample_xy(features: np.ndarray, i: int, window: int = WINDOW_SIZE,
-              horizon: int = FORECAST_HORIZON):
+              horizon: int = FORECAST_HORIZON, channels: int = OUTPUT_CHANNELS):
     """``WeatherGraphDataset.__getitem__`` restated (dataset.py:30-48), F5 included:
     ``x = features[i:i+W].reshape(W*N, 24)`` (time-major rows) and
-    ``y[h*N + n] = features[i+W+1+h, n, :12]`` (horizon-major rows, targets skip t+0)."""
+    ``y[h*N + n] = features[i+W+1+h, n, :C]`` (horizon-major rows, targets skip t+0;
+    ``channels`` = the model's ``output_channels``, 12 in the reference)."""
     n = features.shape[1]
     x = features[i:i + window].reshape(window * n, -1)
-    y = features[i + window + 1:i + window + 1 + horizon, :, :12].reshape(horizon * n, 12)
+    y = features[i + window + 1:i + window + 1 + horizon, :, :channels].reshape(horizon * n, channels)
     return x, y
 
 
