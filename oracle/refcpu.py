@@ -268,12 +268,13 @@ def support_schedule(step: int, batch: int, support: int) -> List[int]:
 
 
 def inner_loop(Pt, Pg, task: TaskData, steps: int, batch: int, support: int, lr: float,
-               max_norm: float, create_graph: bool = False, record=None, dropout=None):
-    """dropout = (seed, p_gcn, p_lstm, global task id) or None."""
+               max_norm: float, create_graph: bool = False, record=None, dropout=None, schedule=None):
+    """dropout = (seed, p_gcn, p_lstm, global task id) or None. schedule: schedule[k] = the window
+    indices of step k (any order, repeats allowed) instead of ``support_schedule(k, batch, support)``."""
     names = list(Pt.keys())
     params = [Pt[k] for k in names]
     for k in range(steps):
-        idx = support_schedule(k, batch, support)
+        idx = support_schedule(k, batch, support) if schedule is None else [int(i) for i in schedule[k]]
         cur = dict(zip(names, params))
         drop = Dropout(dropout[0], dropout[1], dropout[2], dropout[3], k) if dropout else None
         loss, _ = batch_loss(cur, Pg, task, idx, drop)
@@ -289,11 +290,18 @@ def inner_loop(Pt, Pg, task: TaskData, steps: int, batch: int, support: int, lr:
 
 def meta_step(Pt0: Dict[str, torch.Tensor], Pg, tasks: Sequence[TaskData], query_idx,
               steps: int, batch: int, support: int, lr: float, max_norm: float,
-              order: int, query_scale: float = 0.5, dropout=None, task_ids=None):
+              order: int, query_scale: float = 0.5, dropout=None, task_ids=None, windows=None):
     """Returns dict(meta_loss, query_losses, meta_grad (per name, summed over tasks),
     step_records, adapted (per task)). dropout = (seed, p_gcn, p_lstm): masks of inner step k
-    keyed (seed, task_ids[j], k), the query batch's (seed, task_ids[j], steps)."""
+    keyed (seed, task_ids[j], k), the query batch's (seed, task_ids[j], steps).
+    windows: int [steps + 1][tasks][B], the table ``smaml_meta_step`` takes: task j runs step k on
+    windows[k][j] and queries windows[steps][j]; ``query_idx`` and ``support`` are then ignored (may be
+    None). The masks stay keyed by batch position, batch length, step and task id."""
     names = list(Pt0.keys())
+    if windows is not None:
+        windows = np.asarray(windows)
+        if windows.ndim != 3 or windows.shape[0] != steps + 1 or windows.shape[1] != len(tasks):
+            raise ValueError(f"windows {windows.shape} is not [{steps + 1}][{len(tasks)}][B]")
     meta_grad = {k: torch.zeros_like(v) for k, v in Pt0.items()}
     qlosses, records, adapted_all = [], [], []
     for j, task in enumerate(tasks):
@@ -301,10 +309,12 @@ def meta_step(Pt0: Dict[str, torch.Tensor], Pg, tasks: Sequence[TaskData], query
         rec = []
         tid = task_ids[j] if task_ids is not None else j
         dk = (dropout[0], dropout[1], dropout[2], tid) if dropout else None
+        sched = None if windows is None else windows[:steps, j]
+        qidx = query_idx if windows is None else [int(i) for i in windows[steps, j]]
         adapted = inner_loop(dict(zip(names, theta0)), Pg, task, steps, batch, support, lr,
-                             max_norm, create_graph=(order == 2), record=rec, dropout=dk)
+                             max_norm, create_graph=(order == 2), record=rec, dropout=dk, schedule=sched)
         qdrop = Dropout(dropout[0], dropout[1], dropout[2], tid, steps) if dropout else None
-        qloss, _ = batch_loss(adapted, Pg, task, query_idx, qdrop)
+        qloss, _ = batch_loss(adapted, Pg, task, qidx, qdrop)
         scaled = qloss * query_scale
         if order == 2:
             g = torch.autograd.grad(scaled, theta0)
