@@ -44,7 +44,7 @@ typedef struct smaml_ctx smaml_ctx;
  * (smaml_gcn_conv*, smaml_gcn_forward, smaml_relu_mask, smaml_dropout) can run: every dimension positive,
  * input_channels and hidden_channels multiples of 4, lstm_hidden_size 32 / 64 / 128 / 256,
  * lstm_num_layers <= 8, forecast_horizon * output_channels <= 128, output_channels <= input_channels.
- * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_lstm_forward,
+ * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_backward_base, smaml_lstm_forward,
  * smaml_lstm_backward, smaml_head_loss, smaml_meta_step, smaml_inner_loop, smaml_adapt_prepare[_multi],
  * smaml_adapt_steps[_multi], smaml_forecast, smaml_forecast_ensemble) requires in addition
  *   hidden_channels % 16 == 0                        (the layer-0 K segment of the gate-GEMM tile loaders)
@@ -310,6 +310,33 @@ int smaml_adapt_phases(const smaml_ctx* ctx, double* ms, int32_t cap, int32_t* c
  * train_hybrid_maml_v5.py:134). Consumes the saved activations (ESTATE if there are none). */
 int smaml_backward(smaml_ctx* ctx, void* stream, const float* theta, const float* dpred, float* grad);
 
+/* smaml_backward for the most recent smaml_forward, continued through the GCN base: what loss.backward()
+ * computes through HybridSTGCN_LSTM.forward when extract_base_features does NOT run under no_grad, i.e. what
+ * the reference's freeze_base=False / unfreeze_base_model() promise (hybrid_model.py:16-58,126-134) and its
+ * no_grad (F2) withholds. Opt-in: nothing else in the library produces GCN or input gradients.
+ *   grad [P]: exactly smaml_backward's result (the same launches; bitwise equal).
+ *   gcn_grad (device, optional) [Pg]: the layout of smaml_param_layout(which = 1) (conv{k}.bias, then
+ *     conv{k}.lin.weight), overwritten, pads zero: the gradient summed over the samples. 16-byte aligned.
+ *   dx_host (optional): dx_host[s] = device pointer to sample s's d loss / d x [T*N][input_channels], 16-byte
+ *     aligned. gcn_grad and dx_host both NULL: SMAML_EINVAL (call smaml_backward).
+ *   x_host, nsamples: the forward's samples again (the GCN activations are recomputed from them); another
+ *     nsamples: SMAML_ESTATE; NULL or misaligned pointers: SMAML_EINVAL. Other states and errors are
+ *     smaml_backward's; all are checked before anything is launched, the NULL arguments before a device is needed.
+ * After the BPTT, k_lstm_dx0 forms the gradient of the LSTM's layer-0 input from layer 0's gate gradients,
+ * dF = dG0 . W_ih0, applies conv4's ReLU derivative from the saved features and writes the per-sample layout
+ * (one launch; smaml_set_option("dx0_fused", 0) runs the GEMM + smaml_relu_mask + copies it replaces). conv1..
+ * conv3's outputs are then recomputed with the forward's dropout masks (the forward's fused GCN keeps them in
+ * registers), and conv4..conv1 run smaml_gcn_conv_backward's launches over all samples (F3: each sample's rows
+ * < N aggregate over the graph, the rest see their self loop), the masks replayed on the gradient.
+ * Deterministic (fixed-order sums); does not synchronise the stream. Consumes the saved activations like
+ * smaml_backward; a smaml_forecast between the forward and this call leaves it valid. The recomputed
+ * activations and gradient buffers (nsamples*T*N rows x (3 Hc + 2 max(Hc, Cin) + Cin) floats, plus the GCNConv
+ * backward's scratch) are the context's own: they grow only and are freed by smaml_destroy.
+ * Not covered: GCN gradients inside smaml_meta_step / smaml_adapt_steps[_multi], whose feature cache and
+ * distinct-row paths assume a frozen base. */
+int smaml_backward_base(smaml_ctx* ctx, void* stream, const float* theta, const float* const* x_host, int32_t nsamples,
+                        const float* dpred, float* grad, float* gcn_grad, float* const* dx_host);
+
 /* In-place train-mode dropout of one STGCN conv output (model.py:33,36,39,42: after conv
  * layer+1's ReLU, STGCN.forward): x [n] (device) gets the counter-based mask of the GCN site
  * `layer` (0..3), seed `seed`, and the 1/(1-p) scale. */
@@ -450,6 +477,9 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  default: the measured plan -- 3 to 5 regions in sets of 2, where a set
  *                                  of that size is slower per region than one region alone, every other
  *                                  count all at once);
+ *   "dx0_fused":                   smaml_backward_base forms the layer-0 input gradient through conv4's ReLU
+ *                                  with k_lstm_dx0 (1, the default) or with the GEMM, ReLU-mask pass and
+ *                                  per-sample copies it replaces (0; bitwise equal; measurement only);
  *   "adapt_phase_sync":            smaml_adapt_steps synchronises its stream after the feature-cache fill
  *                                  and after the step loop so smaml_adapt_phases reports GPU time (0,
  *                                  the default; measurement only);

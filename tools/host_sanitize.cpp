@@ -406,6 +406,22 @@ int main() {
     CHECK(std::strstr(smaml_last_error(), "ctx is NULL") != nullptr);
     CHECK(smaml_forecast_bytes(nullptr) == 0);
   }
+  // smaml_backward_base's argument checks (nothing launches): no output asked for, NULL inputs, no context
+  {
+    float* some = reinterpret_cast<float*>(0x1000);  // never dereferenced: every call fails before
+    const float* xs[1] = {some};
+    float* dxs[1] = {some};
+    CHECK(smaml_backward_base(nullptr, nullptr, some, xs, 1, some, some, nullptr, nullptr) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "both NULL") != nullptr);
+    CHECK(smaml_backward_base(nullptr, nullptr, nullptr, xs, 1, some, some, some, dxs) == SMAML_EINVAL);
+    CHECK(smaml_backward_base(nullptr, nullptr, some, nullptr, 1, some, some, some, dxs) == SMAML_EINVAL);
+    CHECK(smaml_backward_base(nullptr, nullptr, some, xs, 0, some, some, some, dxs) == SMAML_EINVAL);
+    CHECK(smaml_backward_base(nullptr, nullptr, some, xs, 1, nullptr, some, some, dxs) == SMAML_EINVAL);
+    CHECK(smaml_backward_base(nullptr, nullptr, some, xs, 1, some, nullptr, some, dxs) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "bad backward_base arguments") != nullptr);
+    CHECK(smaml_backward_base(nullptr, nullptr, some, xs, 1, some, some, some, nullptr) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "ctx is NULL") != nullptr);
+  }
   CHECK(smaml_reserve(nullptr, 1, 1) == SMAML_EINVAL);
   CHECK(smaml_set_graph(nullptr, ei.data(), E) == SMAML_EINVAL);
   CHECK(smaml_variant_counts(nullptr, nullptr, 0, nullptr, 0) == SMAML_EINVAL);

@@ -25,7 +25,7 @@ EXPORTS = (
     "smaml_comm_init", "smaml_comm_allreduce", "smaml_comm_destroy", "smaml_variant_counts", "smaml_set_option",
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
-    "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble",
+    "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -95,6 +95,7 @@ _SIGS = {
     "smaml_adapt_steps": ([P, P, P, P, P, I32, I32, I32, PI32, P, F32, F32, F32, F32, F32, P], I32),
     "smaml_timing": ([P, I32], I32),
     "smaml_backward": ([P, P, P, P, P], I32),
+    "smaml_backward_base": ([P, P, P, ctypes.POINTER(P), I32, P, P, P, ctypes.POINTER(P)], I32),
     "smaml_gcn_forward": ([P, P, ctypes.POINTER(P), I32, P], I32),
     "smaml_lstm_forward": ([P, P, P, P, I32, P], I32),
     "smaml_lstm_backward": ([P, P, P, P, P], I32),
@@ -380,6 +381,16 @@ class Context:
 
     def backward(self, stream, theta, dpred, grad):
         check(self._L.smaml_backward(self._h, stream, ptr(theta), ptr(dpred), ptr(grad)))
+
+    def backward_base(self, stream, theta, xs, dpred, grad, gcn_grad=None, dxs=None):
+        """smaml_backward continued through the GCN base (smaml_backward_base) for the forward of the samples
+        ``xs``: ``grad`` [P] as ``backward``; ``gcn_grad`` [Pg] (layout which=1, summed over the samples) and /
+        or ``dxs`` (one [T*N, Cin] tensor per sample: d loss / d x), at least one of the two."""
+        if dxs is not None and len(dxs) != len(xs):
+            raise ValueError(f"{len(dxs)} dx tensors for {len(xs)} samples")
+        check(self._L.smaml_backward_base(self._h, stream, ptr(theta), _ptrs(xs), len(xs), ptr(dpred), ptr(grad),
+                                          ptr(gcn_grad) if gcn_grad is not None else None,
+                                          _ptrs(dxs) if dxs is not None else None))
 
     def gcn_forward(self, stream, xs, feats):
         check(self._L.smaml_gcn_forward(self._h, stream, _ptrs(xs), len(xs), ptr(feats)))

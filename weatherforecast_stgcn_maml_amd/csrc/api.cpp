@@ -268,6 +268,10 @@ struct smaml_ctx {
   // and A_hat^T as CSR (GCNConv backward's aggregation of the t = 0 rows)
   HipBuf ell_c, ell_v, tr_p, tr_c, tr_v;
   HipBuf bw_scratch;  // GCNConv backward: [rows][max(cin, cout)] x 2 floats
+  // smaml_backward_base: conv1..conv3's recomputed activations [3][R][Hc], two gradient buffers
+  // [2][R][max(Hc, Cin0)] and the samples' inputs in one piece [R][Cin0], R = nsamples*T*N (grows only)
+  HipBuf bg_buf;
+  int dx0_fused = 1;  // smaml_set_option("dx0_fused"): k_lstm_dx0 (1) or the GEMM + relu_mask + copies it replaces (0)
   const float* gcn = nullptr;
   // workspace
   HipBuf arena;
@@ -1521,6 +1525,46 @@ int check_device_error(smaml_ctx* c) {
               "results are invalid");
 }
 
+// Backward of z = A_hat x W^T + b over `rows` rows given dz [rows][cout] (smaml_gcn_conv_backward, and every
+// layer of smaml_backward_base). The rows are samples of rps rows each; each sample's first ng rows
+// aggregate over the graph (ng = 0: A_hat = I), the rest see only their self loop (F3). dx [rows][cin]
+// (optional) = A_hat^T (dz W); grad (optional): dW (cout x cin, row-major) at off_w and db (cout) at off_b,
+// summed over all rows, overwritten. Scratch: c->bw_scratch (grown here; grow it before the first launch of
+// a call that must not stall mid-way). Fixed-order sums.
+int gcn_conv_bwd(smaml_ctx* c, hipStream_t s, const float* x, int rows, int rps, int cin, const float* weight, int cout,
+                 const float* dz, int ng, float* dx, float* grad, int64_t off_w, int64_t off_b) {
+  const int64_t half = (int64_t)rows * std::max(cin, cout);
+  HIP_TRY(c->bw_scratch.grow(2 * half * 4));
+  float* t0 = c->bw_scratch.as<float>();
+  float* t1 = t0 + half;
+  if (grad) {
+    // dW = dz^T (A_hat x), db = sum_rows dz: the split-K weight-gradient GEMM with its bias column
+    const float* ax = x;
+    if (ng > 0) {
+      launch_gather_rows(s, x, t0, rows, cin, ng, c->ell_c.as<int32_t>(), c->ell_v.as<float>(), nullptr, nullptr,
+                         nullptr, rps);
+      ax = t0;
+    }
+    Work w = c->w;
+    w.Z = 1;
+    w.drop = Drop{};
+    w.kn = c->kn;
+    launch_wgrad(s, c->d, w, dz, 0, cout, ax, 0, cin, nullptr, 0, 0, rows, 0, grad, 0, off_w, off_w, off_b, -1, true,
+                 false);
+  }
+  if (dx) {
+    // dx = A_hat^T (dz W): the rows past the graph's nodes see only their self loop
+    if (ng > 0) {
+      launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, t1);
+      launch_gather_rows(s, t1, dx, rows, cin, ng, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
+                         c->tr_v.as<float>(), rps);
+    } else {
+      launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, dx);
+    }
+  }
+  return SMAML_OK;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -1762,35 +1806,7 @@ int smaml_gcn_conv_backward(smaml_ctx* c, void* stream, const float* x, int32_t 
   TRY(reserve(c, 1, 1));  // the split-K partial slabs of the weight gradient
   hipStream_t s = (hipStream_t)stream;
   const int ng = plain ? 0 : std::min(rows, c->d.N);
-  const int64_t half = (int64_t)rows * std::max(cin, cout);
-  HIP_TRY(c->bw_scratch.grow(2 * half * 4));
-  float* t0 = c->bw_scratch.as<float>();
-  float* t1 = t0 + half;
-  if (dwb) {
-    // dW = dz^T (A_hat x), db = sum_rows dz: the split-K weight-gradient GEMM with its bias column
-    const float* ax = x;
-    if (ng > 0) {
-      launch_gather_rows(s, x, t0, rows, cin, ng, c->ell_c.as<int32_t>(), c->ell_v.as<float>(), nullptr, nullptr,
-                         nullptr);
-      ax = t0;
-    }
-    Work w = c->w;
-    w.Z = 1;
-    w.drop = Drop{};
-    w.kn = c->kn;
-    launch_wgrad(s, c->d, w, dz, 0, cout, ax, 0, cin, nullptr, 0, 0, rows, 0, dwb, 0, 0, 0,
-                 (int64_t)cout * cin, -1, true, false);
-  }
-  if (dx) {
-    // dx = A_hat^T (dz W): the rows past the graph's nodes see only their self loop
-    if (ng > 0) {
-      launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, t1);
-      launch_gather_rows(s, t1, dx, rows, cin, ng, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
-                         c->tr_v.as<float>());
-    } else {
-      launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, dx);
-    }
-  }
+  TRY(gcn_conv_bwd(c, s, x, rows, rows, cin, weight, cout, dz, ng, dx, dwb, 0, (int64_t)cout * cin));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -2540,6 +2556,8 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->ens_share = (int)value;
   } else if (k == "ens_group" && value >= -1 && value <= 64) {
     c->ens_group = (int)value;
+  } else if (k == "dx0_fused" && (value == 0 || value == 1)) {
+    c->dx0_fused = (int)value;
   } else if (k == "adapt_gcn_batch" && value >= 0 && value <= 256) {
     c->ad_gcn_batch = (int)value;
   } else if (k == "wgrad_group_wgs" && value >= 1) {
@@ -2593,6 +2611,96 @@ int smaml_backward(smaml_ctx* c, void* stream, const float* theta, const float* 
   HIP_TRY(hipMemsetAsync(grad, 0, (size_t)c->po.P * 4, s));
   c->act_B = -1;  // the BPTT overwrites the saved gates with dG
   TRY(run_backward(c, s, theta, 0, grad));
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+int smaml_backward_base(smaml_ctx* c, void* stream, const float* theta, const float* const* x_host, int32_t nsamples,
+                        const float* dpred, float* grad, float* gcn_grad, float* const* dx_host) {
+  // (the checks that need no context first: they run without a device too)
+  if (!gcn_grad && !dx_host)
+    return fail(SMAML_EINVAL, "smaml_backward_base: gcn_grad and dx_host are both NULL (use smaml_backward)");
+  if (!theta || !x_host || nsamples <= 0 || !dpred || !grad)
+    return fail(SMAML_EINVAL, "bad backward_base arguments");
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_backward_base"));
+  if (c->act_B < 1 || c->w.Z != 1)
+    return fail(SMAML_ESTATE, "smaml_backward_base needs the activations of smaml_forward");
+  if (nsamples != c->act_B)
+    return fail(SMAML_ESTATE, "smaml_backward_base: " + std::to_string(nsamples) + " samples, but the forward ran " +
+                                  std::to_string(c->act_B));
+  if (c->w.fcompact) return fail(SMAML_ESTATE, "internal: smaml_forward left compact features");
+  for (int i = 0; i < nsamples; ++i) {
+    if (!x_host[i] || !aligned16(x_host[i])) return fail(SMAML_EINVAL, "sample x pointers must be 16-B aligned");
+    if (dx_host && (!dx_host[i] || !aligned16(dx_host[i])))
+      return fail(SMAML_EINVAL, "sample dx pointers must be 16-B aligned");
+  }
+  if (gcn_grad && !aligned16(gcn_grad)) return fail(SMAML_EINVAL, "gcn_grad must be 16-byte aligned");
+  TRY(ensure_device(c));
+  hipStream_t s = (hipStream_t)stream;
+  const Dims& d = c->d;
+  Work& w = c->w;
+  const int rps = d.T * d.N, R = nsamples * rps;
+  const int Wd = std::max(d.Hc, d.Cin0);
+  const int64_t hsz = (int64_t)R * d.Hc, gsz = (int64_t)R * Wd, xsz = (int64_t)R * d.Cin0;
+  // every buffer before the first launch (a grow releases the old buffer after a device sync)
+  if (c->bg_buf.grow((3 * hsz + 2 * gsz + xsz) * 4) != hipSuccess || c->bw_scratch.grow(2 * gsz * 4) != hipSuccess)
+    return fail(SMAML_ENOMEM, "smaml_backward_base: hipMalloc of the GCN backward's buffers failed (the forward's "
+                              "activations are still valid)");
+  float* h[3] = {c->bg_buf.as<float>(), c->bg_buf.as<float>() + hsz, c->bg_buf.as<float>() + 2 * hsz};
+  float* g = h[2] + hsz;
+  float* gn = g + gsz;
+  float* xcat = gn + gsz;
+  // smaml_backward's part: the same launches in the same order
+  HIP_TRY(hipMemcpyAsync(w.dpred, dpred, (size_t)w.M * d.HfC * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemsetAsync(grad, 0, (size_t)c->po.P * 4, s));
+  c->act_B = -1;  // the BPTT overwrites the saved gates with dG
+  TRY(run_backward(c, s, theta, 0, grad));
+  // conv1..conv3's outputs (post-ReLU, post-dropout) on the per-layer path with the forward's masks (w.drop):
+  // the forward's fused GCN kept them in registers
+  TRY(upload_xtab(c, s, x_host, nsamples));
+  const float* const* xt = nullptr;
+  TRY(xtab_at(c, 0, &xt));
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
+  for (int k = 0; k < 3; ++k)
+    TIMED(c, s, C_GCN, 2.0 * R * c->go.cin[k] * d.Hc,
+          launch_gcn_layer(s, d, k, nsamples, nsamples, k == 0 ? xt : nullptr, k == 0 ? nullptr : h[k - 1], h[k], false,
+                           true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N,
+                           &w.drop));
+  // dZ4 = dF through conv4's ReLU, per sample: layer 0's dG slab (left by the BPTT) times W_ih0
+  const float* Wih0 = theta + c->po.lay[0].wih;
+  const double fl0 = 2.0 * R * 4 * d.H * d.Hc;
+  if (c->dx0_fused) {
+    TIMED(c, s, C_MISC, fl0, launch_lstm_dx0(s, d, w, w.dG, Wih0, w.F, g));
+  } else {  // the composed form it replaces (A/B): GEMM, ReLU mask, T strided copies per sample
+    const int64_t blk = (int64_t)d.N * d.Hc;
+    TIMED(c, s, C_MISC, fl0, {
+      launch_gemm_nn_plain(s, w.dG, d.T * w.M, 4 * d.H, Wih0, d.Hc, gn);
+      launch_relu_mask(s, gn, w.F, hsz);
+      for (int si = 0; si < nsamples; ++si)  // [T][M][Hc] -> [s][T*N][Hc]
+        (void)hipMemcpy2DAsync(g + (int64_t)si * d.T * blk, blk * 4, gn + (int64_t)si * blk, (int64_t)nsamples * blk * 4,
+                               blk * 4, d.T, hipMemcpyDeviceToDevice, s);
+    });
+  }
+  if (gcn_grad) {
+    HIP_TRY(hipMemsetAsync(gcn_grad, 0, (size_t)c->go.total * 4, s));  // the pads stay zero
+    for (int si = 0; si < nsamples; ++si)
+      HIP_TRY(hipMemcpyAsync(xcat + (int64_t)si * rps * d.Cin0, x_host[si], (size_t)rps * d.Cin0 * 4,
+                             hipMemcpyDeviceToDevice, s));
+  }
+  for (int k = 3; k >= 0; --k) {
+    // through the dropout (its mask replayed) and the ReLU after conv k+1; conv4's ReLU is in dZ4 already
+    if (k < 3) launch_drop_relu_grad(s, g, h[k], hsz, w.drop.gcn() ? w.drop.sc_gcn : 1.f);
+    float* dx = k > 0 || dx_host ? gn : nullptr;
+    TRY(gcn_conv_bwd(c, s, k == 0 ? xcat : h[k - 1], R, rps, c->go.cin[k], c->gcn + c->go.w[k], d.Hc, g, d.N, dx, gcn_grad,
+                     c->go.w[k], c->go.b[k]));
+    std::swap(g, gn);
+  }
+  if (dx_host)
+    for (int si = 0; si < nsamples; ++si)
+      HIP_TRY(hipMemcpyAsync(dx_host[si], g + (int64_t)si * rps * d.Cin0, (size_t)rps * d.Cin0 * 4,
+                             hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }

@@ -604,10 +604,17 @@ hipError_t launch_sweep_update(hipStream_t s, float* V, const float* X, float al
                                const BarPlan& bp);
 // ---- GCNConv backward helpers (module API autograd; kernels.hip) ----
 // out[r] = sum_adj w * src[col] for r < n_gather (ELL when csr_p is null, else CSR), src[r] otherwise
+// rps > 0: the rows are samples of rps rows each, and each sample's first n_gather rows gather (default: one)
 void launch_gather_rows(hipStream_t s, const float* src, float* out, int rows, int cols, int n_gather, const int* ell_c,
-                        const float* ell_v, const int* csr_p, const int* csr_c, const float* csr_v);
+                        const float* ell_v, const int* csr_p, const int* csr_c, const float* csr_v, int rps = 0);
 void launch_relu_mask(hipStream_t s, float* g, const float* h, int64_t n);  // g *= (h > 0)
+// g = h > 0 ? sc * g : 0 (n a multiple of 4): the gradient through drop(relu(.)) given its output h
+void launch_drop_relu_grad(hipStream_t s, float* g, const float* h, int64_t n, float sc);
 void launch_gemm_nn_plain(hipStream_t s, const float* A, int rows, int K, const float* W, int ncols, float* out);
+// dZ [B][T*N][Hc] = (dG0 [T][M][4H] . Wih0 [4H][Hc]) * (F [T][M][Hc] > 0) with rows regrouped per sample
+// (k_lstm_dx0: the LSTM's layer-0 input gradient through conv4's ReLU; one task, M = w.M = B*N)
+void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* dG0, const float* Wih0, const float* F,
+                     float* dZ);
 // out[z] = A[z] . W[z]^T (both K-contiguous), Z problems with the given element strides
 void launch_gemm_nt(hipStream_t s, const float* A, int64_t a_zstride, int rows, int K, const float* W,
                     int64_t w_zstride, int ncols, float* out, int64_t o_zstride, int Z);

@@ -8,6 +8,8 @@
 //                      hybrid_model.py:105-115, train_hybrid_maml_v5.py:119,133
 //   k_lstm_bwd_step    BPTT of the cell (loss.backward through LSTM)   train_hybrid_maml_v5.py:134
 //   k_wgrad            dW_ih | dW_hh | db  as a split-K GEMM over B*N*T rows
+//   k_lstm_dx0         d loss / d (LSTM layer-0 input) through conv4's ReLU: the step of loss.backward that
+//                      extract_base_features' no_grad (hybrid_model.py:60-78) cuts off (smaml_backward_base)
 //   k_inner_sgd        clip_grad_norm_(1.0) + SGD(lr)   train_hybrid_maml_v5.py:135-139
 //   k_adamw            clip + AdamW (outer)             train_hybrid_maml_v5.py:174-179,245-249
 //
@@ -2722,25 +2724,28 @@ void launch_wgrad_multi(hipStream_t s, const Work& w, WgradPlan* ps, int n, int 
 // hot path, where the GCN is frozen). Row gather: out[r] = sum over the adjacency list of row r of
 // w * src[col] for r < n_gather (the ELL of A_hat for the forward aggregation, or the CSR of A_hat^T
 // for the backward one), out[r] = src[r] for the other rows. One float4 of one row per thread, fixed
-// summation order (deterministic).
+// summation order (deterministic). rps: rows per sample when the rows are several samples one after
+// another (smaml_backward_base): every sample's first n_gather rows gather within that sample (F3).
 __global__ void k_gather_rows(const float* __restrict__ src, float* __restrict__ out, int rows, int cols,
                               int n_gather, const int* __restrict__ ell_c, const float* __restrict__ ell_v,
                               const int* __restrict__ csr_p, const int* __restrict__ csr_c,
-                              const float* __restrict__ csr_v) {
+                              const float* __restrict__ csr_v, int rps) {
   const int q4 = cols / 4;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)rows * q4) return;
   const int r = (int)(i / q4), k = 4 * (int)(i - (int64_t)r * q4);
+  const int q = r % rps;  // row within its sample: the first n_gather rows of every sample gather
   float4 v;
-  if (r < n_gather) {
+  if (q < n_gather) {
+    const float* sb = src + (int64_t)(r - q) * cols;
     v = f4zero();
     if (csr_p) {
-      for (int e = csr_p[r]; e < csr_p[r + 1]; ++e) v = fma4(csr_v[e], ld4(src + (int64_t)csr_c[e] * cols + k), v);
+      for (int e = csr_p[q]; e < csr_p[q + 1]; ++e) v = fma4(csr_v[e], ld4(sb + (int64_t)csr_c[e] * cols + k), v);
     } else {
 #pragma unroll
       for (int e = 0; e < ELLW; ++e) {
-        const float wv = ell_v[r * ELLW + e];
-        if (wv != 0.f) v = fma4(wv, ld4(src + (int64_t)ell_c[r * ELLW + e] * cols + k), v);
+        const float wv = ell_v[q * ELLW + e];
+        if (wv != 0.f) v = fma4(wv, ld4(sb + (int64_t)ell_c[q * ELLW + e] * cols + k), v);
       }
     }
   } else {
@@ -2750,10 +2755,10 @@ __global__ void k_gather_rows(const float* __restrict__ src, float* __restrict__
 }
 
 void launch_gather_rows(hipStream_t s, const float* src, float* out, int rows, int cols, int n_gather, const int* ell_c,
-                        const float* ell_v, const int* csr_p, const int* csr_c, const float* csr_v) {
+                        const float* ell_v, const int* csr_p, const int* csr_c, const float* csr_v, int rps) {
   const int64_t n = (int64_t)rows * (cols / 4);
   k_gather_rows<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, out, rows, cols, n_gather, ell_c, ell_v, csr_p,
-                                                            csr_c, csr_v);
+                                                            csr_c, csr_v, rps > 0 ? rps : rows);
 }
 
 // g *= (h > 0): the ReLU derivative taken from the (post-ReLU, post-dropout) activation h
@@ -2768,10 +2773,74 @@ void launch_relu_mask(hipStream_t s, float* g, const float* h, int64_t n) {
   k_relu_mask<<<nb, 256, 0, s>>>(g, h, n);
 }
 
+// g = h > 0 ? sc * g : 0 from h = drop(relu(z)): the masked activation is zero exactly where the mask
+// dropped the element or the ReLU was off, so this one test replays the forward's mask and applies the
+// ReLU derivative, and the kept elements take the mask's 1 / (1 - p) scale (sc = 1 without dropout).
+__global__ void k_drop_relu_grad(float* __restrict__ g, const float* __restrict__ h, int64_t n4, float sc) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 hv = ld4(h + 4 * i);
+    float4 gv = ld4(g + 4 * i);
+    gv.x = hv.x > 0.f ? sc * gv.x : 0.f;
+    gv.y = hv.y > 0.f ? sc * gv.y : 0.f;
+    gv.z = hv.z > 0.f ? sc * gv.z : 0.f;
+    gv.w = hv.w > 0.f ? sc * gv.w : 0.f;
+    st4(g + 4 * i, gv);
+  }
+}
+
+void launch_drop_relu_grad(hipStream_t s, float* g, const float* h, int64_t n, float sc) {
+  const int64_t n4 = n / 4;  // (n = rows * Hc, Hc a multiple of 4)
+  int nb = (int)((n4 + 255) / 256);
+  if (nb > 4096) nb = 4096;
+  k_drop_relu_grad<<<nb, 256, 0, s>>>(g, h, n4, sc);
+}
+
 // out = A . W  (A [rows][K] row-major, W [K][ncols] row-major): k_gemm_nn on one problem
 void launch_gemm_nn_plain(hipStream_t s, const float* A, int rows, int K, const float* W, int ncols, float* out) {
   dim3 grid((rows + CfgNN::BM - 1) / CfgNN::BM, (ncols + CfgNN::BN - 1) / CfgNN::BN, 1);
   k_gemm_nn<<<grid, CfgNN::NTH, 0, s>>>(A, 0, rows, K, W, 0, 0, ncols, out, 0);
+}
+
+// Gradient of the LSTM's layer-0 input carried through conv4's ReLU into the per-sample layout of the GCN
+// backward (smaml_backward_base), over all T*M rows of one task in one launch:
+//   dZ4[s][t*N + n][:] = (dG0[t][s*N + n][0:4H] . W_ih0[4H][Hc]) * (F[t][s*N + n][:] > 0)
+// A = layer 0's dG slab as the BPTT leaves it, B = W_ih0 as stored in theta ([4H][Hc] row-major: k_gemm_nn's
+// orientation and tile), F = the saved GCN features [T][M][Hc] (conv4's post-ReLU output; no dropout after
+// conv4). The epilogue replaces a relu_mask pass over the product and T strided copies per sample.
+__global__ __launch_bounds__(NT) void k_lstm_dx0(const float* __restrict__ dG0, const float* __restrict__ Wih0,
+                                                 const float* __restrict__ F, float* __restrict__ dZ, int T, int M,
+                                                 int N, int K, int Hc, FastDiv mdiv, FastDiv ndiv) {
+  __shared__ float smem[CfgNN::SMEM_FLOATS];
+  const int rows = T * M;
+  RowMajorKC la{dG0, rows, K};
+  RowMajorMC lb{Wih0, K, Hc};
+  const int m0 = blockIdx.x * CfgNN::BM, n0 = blockIdx.y * CfgNN::BN;
+  Acc<CfgNN> acc;
+  acc.zero();
+  gemm_mainloop<CfgNN>(la, lb, m0, n0, 0, K, acc, smem);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = m0 + acc_row<CfgNN>(0, r);
+    if (m >= rows) continue;
+    const int t = (int)mdiv.div((uint32_t)m), q = m - t * M;  // row m = t*M + s*N + n
+    const int sidx = (int)ndiv.div((uint32_t)q), n = q - sidx * N;
+    const float* f = F + (int64_t)m * Hc;
+    float* o = dZ + (((int64_t)sidx * T + t) * N + n) * Hc;
+#pragma unroll
+    for (int j = 0; j < CfgNN::WTN; ++j) {
+      const int c = n0 + acc_col<CfgNN>(j);
+      if (c < Hc) o[c] = f[c] > 0.f ? acc.v[0][j][r] : 0.f;
+    }
+  }
+}
+
+void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* dG0, const float* Wih0, const float* F,
+                     float* dZ) {
+  static_assert(CfgNN::WTM == 1, "k_lstm_dx0's epilogue walks one 32-row tile per wave");
+  const int rows = d.T * w.M;
+  dim3 grid((rows + CfgNN::BM - 1) / CfgNN::BM, (d.Hc + CfgNN::BN - 1) / CfgNN::BN, 1);
+  k_lstm_dx0<<<grid, CfgNN::NTH, 0, s>>>(dG0, Wih0, F, dZ, d.T, w.M, d.N, 4 * d.H, d.Hc, FastDiv((uint32_t)w.M),
+                                         FastDiv((uint32_t)d.N));
 }
 
 // out[z] = A[z] . W[z]^T, both operands K-contiguous ([rows][K], [ncols][K]); the batch-1 forward's

@@ -23,6 +23,17 @@ call draws a fresh mask seed from the global torch RNG (as ``nn.Dropout`` draws 
 the backward reuses the forward's masks. ``eval()`` (or p = 0) runs without dropout.
 For whole meta-steps use ``weatherforecast_stgcn_maml_amd.maml`` (run entirely inside the
 library).
+
+Training the base (opt-in). The reference's ``freeze_base=False`` / ``unfreeze_base_model()`` set
+``requires_grad`` on the base but its ``extract_base_features`` still runs under ``no_grad``, so the base
+never trains; that stays the default here. ``HybridSTGCN_LSTM(..., base_grad=True)`` or
+``enable_base_grad()`` routes ``forward`` through ``_HybridBaseFn``, whose backward is
+``smaml_backward_base``: the BPTT as before, then the LSTM's layer-0 input gradient through conv4's ReLU
+(one HIP kernel) and the GCN backward over conv4..conv1 with the forward's dropout masks. It fills ``.grad``
+of ``base_stgcn.conv{1..4}.{bias, lin.weight}`` (those with ``requires_grad``) and of ``x`` when
+``x.requires_grad`` (input saliency); ``base_stgcn.output_layer`` is not on the hybrid path and gets none.
+The switch is not part of ``state_dict``. Not covered: ``maml`` meta-steps and ``adapt`` (their feature
+cache and distinct-row paths assume a frozen base).
 """
 from __future__ import annotations
 
@@ -72,6 +83,38 @@ class _HybridFn(torch.autograd.Function):
         return (None, None, None, None, None, None, *[g[n] for n in fctx.names])
 
 
+class _HybridBaseFn(torch.autograd.Function):
+    """``_HybridFn`` with the backward continued through the GCN base (``smaml_backward_base``): gradients for
+    ``base_stgcn.conv{1..4}.{bias, lin.weight}`` (those that require grad) and for ``x`` (when it does) beside
+    the LSTM / head gradients. ``tensors`` = the trainable tensors, then the eight conv tensors."""
+
+    @staticmethod
+    def forward(fctx, x, lib_ctx, dims, theta, names, gnames, drop, *tensors):
+        pred = torch.empty(dims.num_nodes * dims.forecast_horizon, dims.output_channels, device=x.device)
+        _forward(lib_ctx, theta, [x], pred, drop)
+        fctx.save_for_backward(x)
+        fctx.lib_ctx, fctx.dims, fctx.theta, fctx.names, fctx.gnames = lib_ctx, dims, theta, names, gnames
+        return pred
+
+    @staticmethod
+    def backward(fctx, gpred):
+        (x,) = fctx.saved_tensors
+        nt, st = len(fctx.names), _capi.stream_ptr(torch)
+        need_g = fctx.needs_input_grad[7 + nt:]
+        grad = torch.empty_like(fctx.theta)
+        gflat = torch.empty(params.gcn_layout(fctx.dims)[1], device=x.device) if any(need_g) else None
+        dx = torch.empty_like(x) if fctx.needs_input_grad[0] else None
+        gpred = gpred.contiguous().float()
+        if gflat is None and dx is None:  # only LSTM / head tensors require grad
+            fctx.lib_ctx.backward(st, fctx.theta, gpred, grad)
+        else:
+            fctx.lib_ctx.backward_base(st, fctx.theta, [x], gpred, grad, gflat, None if dx is None else [dx])
+        g = params.unpack(grad, fctx.dims)
+        gg = params.unpack(gflat, fctx.dims, 1) if gflat is not None else {}
+        return (dx, None, None, None, None, None, None, *[g[n] for n in fctx.names],
+                *[gg[n] if need else None for n, need in zip(fctx.gnames, need_g)])
+
+
 class LSTMParams(nn.Module):
     """Parameter container with ``nn.LSTM``'s names, shapes and init
     (``weight_ih_l{k}`` [4H, in], ``weight_hh_l{k}`` [4H, H], ``bias_ih_l{k}``,
@@ -108,8 +151,9 @@ class LSTMParams(nn.Module):
 
 class HybridSTGCN_LSTM(nn.Module):
     def __init__(self, base_stgcn, lstm_hidden_size=64, lstm_num_layers=2, lstm_dropout=0.2,
-                 out_channels=12, forecast_horizon=8, freeze_base=True):
+                 out_channels=12, forecast_horizon=8, freeze_base=True, *, base_grad=False):
         super().__init__()
+        self.base_grad = bool(base_grad)  # opt-in: gradients through the GCN base (not in state_dict)
         self.forecast_horizon = forecast_horizon
         self.out_channels = out_channels
         self.lstm_hidden_size = lstm_hidden_size
@@ -228,6 +272,11 @@ class HybridSTGCN_LSTM(nn.Module):
         x = x.contiguous().float()
         named = self._trainable_params()
         drop = self._drop()
+        if self.base_grad and torch.is_grad_enabled():
+            gnamed = self._gcn_params()
+            if x.requires_grad or any(p.requires_grad for _, p in named + gnamed):
+                return _HybridBaseFn.apply(x, ctx, dims, theta, [n for n, _ in named], [n for n, _ in gnamed], drop,
+                                           *[p for _, p in named + gnamed])
         if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
             return _HybridFn.apply(x, ctx, dims, theta, [n for n, _ in named], drop, *[p for _, p in named])
         pred = torch.empty(dims.num_nodes * dims.forecast_horizon, dims.output_channels, device=x.device)
@@ -239,6 +288,14 @@ class HybridSTGCN_LSTM(nn.Module):
         trainable.extend(self.lstm.parameters())
         trainable.extend(self.output_layer.parameters())
         return trainable
+
+    def enable_base_grad(self, flag=True):
+        """Route ``forward`` through the backward that continues into the GCN base (``smaml_backward_base``):
+        the conv parameters that require grad (``unfreeze_base_model()`` / ``freeze_base=False``) and ``x``
+        (``x.requires_grad_()``) then receive gradients. Off (the default): the reference's behaviour, the
+        base runs under no_grad (F2)."""
+        self.base_grad = bool(flag)
+        return self
 
     def freeze_base_model(self):
         for p in self.base_stgcn.parameters():
