@@ -46,7 +46,7 @@ typedef struct smaml_ctx smaml_ctx;
  * lstm_num_layers <= 8, forecast_horizon * output_channels <= 128, output_channels <= input_channels.
  * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_backward_base, smaml_lstm_forward,
  * smaml_lstm_backward, smaml_head_loss, smaml_meta_step, smaml_inner_loop, smaml_adapt_prepare[_multi],
- * smaml_adapt_steps[_multi], smaml_forecast, smaml_forecast_ensemble) requires in addition
+ * smaml_adapt_steps[_multi, _full], smaml_forecast, smaml_forecast_ensemble) requires in addition
  *   hidden_channels % 16 == 0                        (the layer-0 K segment of the gate-GEMM tile loaders)
  *   (forecast_horizon * output_channels) % 4 == 0    (16-byte reads of prediction rows)
  * and returns SMAML_EINVAL naming the dimension otherwise, before it allocates or launches anything. */
@@ -302,6 +302,45 @@ int smaml_adapt_prepare_multi(smaml_ctx* ctx, void* stream, int32_t nregions, co
  * step computed itself (outside the batched fill). Measurement only; no reference counterpart. */
 int smaml_adapt_phases(const smaml_ctx* ctx, double* ms, int32_t cap, int32_t* count, int64_t* filled);
 
+/* Whole-model regional adaptation: smaml_adapt_steps with the GCN base trained too -- what the reference's
+ * adaptation script announces (freeze_base=False, one optimiser "for ALL parameters (STGCN + LSTM)") and its
+ * no_grad in extract_base_features withholds (F2). One region: task 0 of smaml_set_tasks. Step k: forward in
+ * train mode (the masks of smaml_set_dropout, task id 0, step step0 + k), MSE, the backward through the head,
+ * the LSTM and conv4..conv1, clip_grad_norm_(max_norm) over ALL gradients jointly (the trainable vector's and
+ * the GCN vector's; squared sum in double, fixed order), torch.optim.Adam with coupled L2 weight decay at
+ * lr_dev[k], Adam step step0 + k + 1, on both vectors (the element arithmetic of smaml_adapt_steps).
+ *   theta, m, v [P] (layout which = 0) and gcn, gcn_m, gcn_v [Pg] (layout which = 1): device, 16-byte aligned,
+ *     updated in place; the pads of both layouts stay zero.
+ *   windows_host [nsteps][batch], lr_dev [nsteps], step0, losses [nsteps]: as smaml_adapt_steps. Any batch >= 1.
+ *   norms (device, optional) [nsteps]: the joint gradient norm of each step before clipping.
+ * gcn becomes the context's GCN parameter vector exactly as after smaml_set_gcn_params(gcn) (no earlier
+ * smaml_set_gcn_params is needed), so a following smaml_forecast, smaml_meta_step(order 0), smaml_forward or
+ * smaml_adapt_steps sees the adapted base. The batch-1 feature cache of smaml_adapt_steps is invalidated and
+ * is neither allocated nor read here (it describes a frozen base). A pending smaml_forward / smaml_backward
+ * pair is consumed. The forward keeps conv1..conv3's outputs for the backward (k_gcn_mlp's keep variant where
+ * the fused GCN runs, else the per-layer launches write them in place), the layer-to-layer gradient is a GEMM,
+ * a gather and a mask pass per layer (option "gcn_dz_fused" = 1: one GEMM with the mask in its epilogue plus a
+ * gather over the t = 0 rows, k_gcn_dz), and the clip and Adam of both vectors are two launches (k_sqsum2,
+ * k_adam_l2_joint). Option "gcn_keep" = 0 recomputes the kept outputs instead. The kept activations and gradient buffers (batch*T*N rows x 5 Hc floats and smaller
+ * pieces) are the context's own: they grow only and are freed by smaml_destroy.
+ * Checked before anything is allocated or launched, the NULL arguments, alignment and counts before a device
+ * is needed: NULL arguments (norms may be NULL), alignment, nsteps and batch positive, step0 non-negative
+ * (SMAML_EINVAL); the dims of the LSTM path, the graph and the tasks (SMAML_EINVAL / SMAML_ESTATE); the window
+ * range (SMAML_EINVAL). Every buffer is grown before the first launch: SMAML_ENOMEM leaves all six vectors
+ * untouched. Deterministic (fixed-order sums); does not synchronise the stream.
+ * Not covered: smaml_adapt_steps_multi with a trained base, GCN gradients inside smaml_meta_step. */
+int smaml_adapt_steps_full(smaml_ctx* ctx, void* stream, float* theta, float* m, float* v, float* gcn, float* gcn_m,
+                           float* gcn_v, int32_t step0, int32_t nsteps, int32_t batch, const int32_t* windows_host,
+                           const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                           float max_norm, float* losses, float* norms);
+
+/* Host-side launch counters of the last smaml_adapt_steps_full call: [0] steps, [1] fused keeping-GCN launches
+ * (k_gcn_mlp's keep variant), [2] per-layer keeping-GCN launches (k_gcn_layer over all rows writing conv k's
+ * output where the backward reads it; the t = 0 launches beside the fused kernel are not counted), [3] fused
+ * k_gcn_dz launches, [4] launches of the composed form (GEMM, gather, mask), [5] launches recomputing conv1..
+ * conv3 (option "gcn_keep" = 0). Writes min(cap, count) entries; *count = 6. Measurement and tests only. */
+int smaml_adapt_full_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
+
 /* ---- finer-grained operators (the module pieces callers compose) -------- */
 
 /* Backward of the most recent smaml_forward (same theta): dpred [nsamples][N*Hf][C]
@@ -332,7 +371,8 @@ int smaml_backward(smaml_ctx* ctx, void* stream, const float* theta, const float
  * smaml_backward; a smaml_forecast between the forward and this call leaves it valid. The recomputed
  * activations and gradient buffers (nsamples*T*N rows x (3 Hc + 2 max(Hc, Cin) + Cin) floats, plus the GCNConv
  * backward's scratch) are the context's own: they grow only and are freed by smaml_destroy.
- * Not covered: GCN gradients inside smaml_meta_step / smaml_adapt_steps[_multi], whose feature cache and
+ * smaml_adapt_steps_full runs whole steps of one region with this gradient inside the library.
+ * Not covered: GCN gradients inside smaml_meta_step / smaml_adapt_steps_multi, whose feature cache and
  * distinct-row paths assume a frozen base. */
 int smaml_backward_base(smaml_ctx* ctx, void* stream, const float* theta, const float* const* x_host, int32_t nsamples,
                         const float* dpred, float* grad, float* gcn_grad, float* const* dx_host);
@@ -480,6 +520,15 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *   "dx0_fused":                   smaml_backward_base forms the layer-0 input gradient through conv4's ReLU
  *                                  with k_lstm_dx0 (1, the default) or with the GEMM, ReLU-mask pass and
  *                                  per-sample copies it replaces (0; bitwise equal; measurement only);
+ *   "gcn_keep":                    smaml_adapt_steps_full's forward keeps conv1..conv3's outputs for the
+ *                                  backward (1, the default) or runs the frozen-base forward and recomputes
+ *                                  them per layer as smaml_backward_base does (0; equal within tolerance,
+ *                                  not bitwise: the fused and per-layer K orders differ);
+ *   "gcn_dz_fused":                smaml_adapt_steps_full forms each layer-to-layer gradient of the base
+ *                                  with the GEMM, gather and mask passes over all rows (0, the default) or
+ *                                  with k_gcn_dz, one GEMM with the mask in its epilogue plus a gather over
+ *                                  the t = 0 rows (1; bitwise equal; measured 0.8 % slower per step at
+ *                                  config-4 shapes, so it ships off);
  *   "adapt_phase_sync":            smaml_adapt_steps synchronises its stream after the feature-cache fill
  *                                  and after the step loop so smaml_adapt_phases reports GPU time (0,
  *                                  the default; measurement only);

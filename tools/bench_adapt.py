@@ -18,6 +18,21 @@ later epochs: each is one repetition; --epochs 6 gives five), the set-up time (w
 smaml_adapt_prepare[_multi]), the bytes the set-up took, the ratio sequential / lockstep, and with
 --timing the per-category kernel time of one more lockstep epoch. --adapt-group g runs g regions per
 launch set (option adapt_group); --no-sequential skips the yardstick.
+
+--train-base: whole-model adaptation (smaml_adapt_steps_full: the GCN base trained inside the step) at config-4
+shapes, batch 1, no dropout, later epochs (every buffer and cache warm), ms per step. Arms, alternating in one
+process, each repetition --steps steps timed on the host around a device synchronise:
+  full                smaml_adapt_steps_full, default options
+  full_keep0          ... option gcn_keep = 0 (frozen-base forward + recompute of conv1..conv3)
+  full_dz_fused       ... option gcn_dz_fused = 1 (k_gcn_dz instead of GEMM + gather + mask per layer)
+  module              yardstick (a): the same steps through HybridSTGCN_LSTM(base_grad=True) with MSE,
+                      clip_grad_norm_(1.0) and torch.optim.Adam(weight_decay), windows already on the device
+  frozen              yardstick (b): smaml_adapt_steps (frozen base, feature cache warm): what training the base
+                      costs on top of it, not a race
+Medians of --reps repetitions after --warmup, with min and max; then the event time per timing category of one
+more repetition of each library arm (gcn_layer: the GCN forward and recompute; misc: k_lstm_dx0, k_gcn_dz or its
+composed form, the weight re-split, k_sqsum2 + k_adam_l2_joint). The lines go to stdout and to --log
+(default profiles/adapt_full_bench.log); ONE JSON line last.
 """
 from __future__ import annotations
 
@@ -44,7 +59,13 @@ def main():
     p.add_argument("--adapt-group", type=int, default=-1, help="option adapt_group of the lockstep run (-1: the default plan)")
     p.add_argument("--no-sequential", action="store_true")
     p.add_argument("--timing", action="store_true", help="one more lockstep epoch with per-category kernel timing")
+    p.add_argument("--train-base", action="store_true", help="whole-model adaptation arms and yardsticks (see above)")
+    p.add_argument("--steps", type=int, default=48, help="--train-base: steps per timed repetition")
+    p.add_argument("--reps", type=int, default=5, help="--train-base: timed repetitions per arm")
+    p.add_argument("--log", default=os.path.join(REPO, "profiles", "adapt_full_bench.log"))
     a = p.parse_args()
+    if a.train_base:
+        return train_base_main(a)
     if a.regions > 0:
         return regions_main(a)
     import torch
@@ -150,6 +171,155 @@ REGION_NAMES = ("Amazon", "Thailand", "Moscow", "Delhi", "Indonesia", "NorthSibe
 def spread(xs):
     xs = sorted(xs)
     return {"min": xs[0], "median": xs[len(xs) // 2], "max": xs[-1], "n": len(xs)} if xs else None
+
+
+def train_base_main(a):
+    import torch
+
+    from weatherforecast_stgcn_maml_amd import _capi, adapt, params, synth
+    from weatherforecast_stgcn_maml_amd.config import SEED, ModelDims
+    from weatherforecast_stgcn_maml_amd.graph import build_spatial_graph
+    from weatherforecast_stgcn_maml_amd.hybrid_model import HybridSTGCN_LSTM
+    from weatherforecast_stgcn_maml_amd.model import STGCN
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_adapt --train-base needs a HIP device (no CPU fallback)")
+    d = ModelDims(num_nodes=441, hidden_channels=256)
+    T, Hf, N, C = d.window_size, d.forecast_horizon, d.num_nodes, d.output_channels
+    lats, lons = synth.region_grid(n_lat=21, n_lon=21)
+    ei, _, _ = build_spatial_graph(lats, lons, 4)
+    P = synth.init_params(SEED, d, gcn_bias_scale=0.1)
+    names = [k for k in P if k.startswith(("lstm.", "output_layer."))]
+    conv = [k for k in P if k.startswith("base_stgcn.conv")]
+    dev = torch.device("cuda:0")
+    n_steps = a.steps
+    T_total = n_steps + T + Hf
+    stream_t = torch.from_numpy(np.ascontiguousarray(synth.make_features(synth.task_seed(0), N, T_total))).to(dev)
+    lr, wd = adapt.climate_optimizer_config(a.region, 0.0006)
+    st = _capi.stream_ptr(torch)
+    rng = np.random.default_rng(SEED)
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"build: {_capi.build_info()}")
+    say(f"config-4 shapes N={N} T={T} Hc={d.hidden_channels} LSTM {d.lstm_num_layers}x{d.lstm_hidden_size}, batch 1, "
+        f"p = 0, {n_steps} steps per repetition, {a.reps} repetitions after {a.warmup} warm-up, Adam lr {lr:g} wd {wd:g}")
+
+    class LibArm:
+        def __init__(self, full, options=()):
+            self.full = full
+            self.ctx = _capi.Context(d, 0)
+            for k, v in options:
+                self.ctx.set_option(k, v)
+            self.ctx.set_graph(ei)
+            self.g = params.pack({k: P[k] for k in conv}, d, which=1, device=dev)
+            self.ctx.set_gcn_params(self.g)
+            self.th = params.pack({k: P[k] for k in names}, d, which=0, device=dev)
+            self.ctx.set_tasks([stream_t])
+            self.ctx.set_task_ids([0])
+            self.vecs = [torch.zeros_like(self.th), torch.zeros_like(self.th), torch.zeros_like(self.g),
+                         torch.zeros_like(self.g)]
+            self.losses = torch.empty(n_steps, device=dev)
+            self.lr_dev = torch.full((n_steps,), lr, device=dev, dtype=torch.float32)
+            self.step = 0
+
+        def run(self, order):
+            m, v, gm, gv = self.vecs
+            w = order.reshape(n_steps, 1)
+            if self.full:
+                self.ctx.adapt_steps_full(st, self.th, m, v, self.g, gm, gv, self.step, w, self.lr_dev, (0.9, 0.999),
+                                          1e-8, wd, adapt.MAX_GRAD_NORM, self.losses)
+            else:
+                self.ctx.adapt_steps(st, self.th, m, v, self.step, w, self.lr_dev, (0.9, 0.999), 1e-8, wd,
+                                     adapt.MAX_GRAD_NORM, self.losses)
+            self.step += n_steps
+
+    class ModuleArm:
+        def __init__(self):
+            base = STGCN(d.input_channels, d.hidden_channels, C, T, Hf, dropout_rate=0.0)
+            self.m = HybridSTGCN_LSTM(base, d.lstm_hidden_size, d.lstm_num_layers, 0.0, C, Hf, freeze_base=False,
+                                      base_grad=True)
+            self.m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+            self.m = self.m.to(dev).train()
+            self.eig = torch.from_numpy(np.ascontiguousarray(ei)).to(dev)
+            self.ps = [q for q in self.m.parameters() if q.requires_grad]
+            self.opt = torch.optim.Adam(self.ps, lr=lr, weight_decay=wd)
+            self.losses = torch.empty(n_steps, device=dev)
+
+        def run(self, order):
+            for k, i in enumerate(order):
+                i = int(i)
+                x = stream_t[i:i + T].reshape(T * N, -1)
+                y = stream_t[i + T + 1:i + T + 1 + Hf, :, :C].reshape(Hf * N, C)
+                self.opt.zero_grad()
+                loss = torch.nn.functional.mse_loss(self.m(x, self.eig), y)
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(self.ps, adapt.MAX_GRAD_NORM)
+                self.opt.step()
+                self.losses[k] = loss.detach()
+
+    arms = {"full": LibArm(True), "full_keep0": LibArm(True, (("gcn_keep", 0),)),
+            "full_dz_fused": LibArm(True, (("gcn_dz_fused", 1),)), "module": ModuleArm(), "frozen": LibArm(False)}
+    times = {k: [] for k in arms}
+    first_loss = {}
+    for rep in range(a.warmup + a.reps):
+        order = rng.permutation(n_steps).astype(np.int32)
+        for k, arm in arms.items():  # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            arm.run(order)
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3 / n_steps)
+            if rep == 0:
+                first_loss[k] = float(arm.losses.double().mean().item())
+
+    def stats(v):
+        return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+
+    res = {k: stats(v) for k, v in times.items()}
+    say("--- ms per step (host time around a device synchronise)")
+    for k, s_ in res.items():
+        say(f"  {k:18s} {s_['median']:9.4f}  (min {s_['min']:.4f}, max {s_['max']:.4f})   first-repetition mean loss "
+            f"{first_loss[k]:.6f}")
+
+    def outside(fast, slow):  # the faster arm's worst repetition still beats the slower arm's best
+        return bool(res[fast]["max"] < res[slow]["min"])
+
+    verdict = {
+        "full_vs_module": {"ratio": res["module"]["median"] / res["full"]["median"], "outside_spread": outside("full", "module")},
+        "keep_vs_recompute": {"ratio": res["full_keep0"]["median"] / res["full"]["median"],
+                              "outside_spread": outside("full", "full_keep0")},
+        "dz_fused_vs_composed": {"ratio": res["full"]["median"] / res["full_dz_fused"]["median"],
+                                 "outside_spread": outside("full_dz_fused", "full")},
+        "base_training_costs_x_frozen": res["full"]["median"] / res["frozen"]["median"],
+    }
+    for k, v in verdict.items():
+        say(f"  {k}: {v}")
+    # event time per category, one more repetition of each library arm
+    cats = {}
+    order = rng.permutation(n_steps).astype(np.int32)
+    for k, arm in arms.items():
+        if k == "module":
+            continue
+        arm.ctx.timing(True)
+        arm.run(order)
+        cats[k] = {c: {"us_per_step": t["ms"] * 1e3 / n_steps, "launches_per_step": t["launches"] / n_steps}
+                   for c, t in arm.ctx.timing_collect().items() if t["launches"]}
+        arm.ctx.timing(False)
+        say(f"--- event time per step, {k}: " + ", ".join(f"{c} {t['us_per_step']:.1f} us ({t['launches_per_step']:.1f} launches)"
+                                                         for c, t in cats[k].items()))
+    stats_full = arms["full"].ctx.adapt_full_stats()
+    say(json.dumps({"metric": "whole-model adaptation, ms per batch-1 step at config-4 shapes (median)",
+                    "value": res["full"]["median"], "unit": "ms/step", "higher_is_better": False, "steps": n_steps,
+                    "reps": a.reps, "ms_per_step": res, "verdict": verdict, "event_us_per_step": cats,
+                    "adapt_full_stats": stats_full, "first_repetition_mean_loss": first_loss}))
+    os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+    with open(a.log, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def regions_main(a):

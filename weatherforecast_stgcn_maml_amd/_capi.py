@@ -26,6 +26,7 @@ EXPORTS = (
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
     "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
+    "smaml_adapt_steps_full", "smaml_adapt_full_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -125,6 +126,10 @@ _SIGS = {
     "smaml_adapt_prepare_multi": ([P, P, I32, PI32, I32], I32),
     "smaml_forecast_ensemble": ([P, P, P, I32, PI32, I32, I32, I32, F32, F32, ctypes.c_uint32, PF32, P, P, P, P], I32),
 }
+_SIGS["smaml_adapt_steps_full"] = ([P, P, P, P, P, P, P, P, I32, I32, I32, PI32, P, F32, F32, F32, F32, F32, P, P], I32)
+_SIGS["smaml_adapt_full_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_adapt_full_stats order (launch counters of the last smaml_adapt_steps_full call)
+ADAPT_FULL_STATS = ("steps", "gcn_keep_fused", "gcn_keep_layer", "gcn_dz_fused", "gcn_dz_composed", "gcn_recompute")
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
 
@@ -308,6 +313,28 @@ class Context:
         check(self._L.smaml_adapt_steps(self._h, stream, ptr(theta), ptr(m), ptr(v), int(step0), w.shape[0],
                                         w.shape[1], w.ctypes.data_as(PI32), ptr(lr_dev), float(betas[0]),
                                         float(betas[1]), float(eps), float(wd), float(max_norm), ptr(losses)))
+
+    def adapt_steps_full(self, stream, theta, m, v, gcn, gcn_m, gcn_v, step0, windows: np.ndarray, lr_dev, betas, eps,
+                         wd, max_norm, losses, norms=None):
+        """``adapt_steps`` with the GCN base trained too (smaml_adapt_steps_full): ``gcn`` / ``gcn_m`` / ``gcn_v``
+        [Pg] (layout which = 1) are updated in place like ``theta`` / ``m`` / ``v``, the clip is over both
+        gradients jointly, and ``gcn`` becomes the context's GCN parameter vector. ``norms`` [nsteps]
+        (device, optional): each step's joint gradient norm before clipping."""
+        w = np.ascontiguousarray(windows, dtype=np.int32)
+        self._gcn = gcn
+        check(self._L.smaml_adapt_steps_full(self._h, stream, ptr(theta), ptr(m), ptr(v), ptr(gcn), ptr(gcn_m),
+                                             ptr(gcn_v), int(step0), w.shape[0], w.shape[1], w.ctypes.data_as(PI32),
+                                             ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps), float(wd),
+                                             float(max_norm), ptr(losses), ptr(norms) if norms is not None else None))
+
+    def adapt_full_stats(self):
+        """{counter: launches} of the last adapt_steps_full call (host counters, no sync)."""
+        n = len(ADAPT_FULL_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_adapt_full_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(ADAPT_FULL_STATS)}
 
     def adapt_prepare(self, stream, batch=1):
         """Workspace + per-window feature cache for adapt_steps, allocated and touched now (no compute)."""

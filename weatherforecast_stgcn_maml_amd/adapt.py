@@ -91,16 +91,22 @@ class AdaptResult:
     val_loss: float = float("nan")
     n_train: int = 0
     n_val: int = 0
+    gcn: Optional[torch.Tensor] = None  # train_base: the adapted GCN vector (params.unpack(gcn, dims, 1))
 
 
 def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_name: str, epochs: int = 15,
           max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
           val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
-          dropout_seed: int = 0, orders=None) -> AdaptResult:
+          dropout_seed: int = 0, orders=None, train_base: bool = False) -> AdaptResult:
     """``dropout`` = (STGCN dropout_rate, lstm_dropout) of the train-mode steps (the reference
     adapts in train mode: (0.2, 0.2)); validation runs without dropout (eval mode).
     ``orders``: optional per-epoch sample permutations of the training windows (default: drawn
-    from the global torch RNG as the reference's shuffling DataLoader draws them)."""
+    from the global torch RNG as the reference's shuffling DataLoader draws them).
+    ``train_base``: fine-tune the GCN base too, as the reference's ``freeze_base=False`` and its optimiser
+    "for ALL parameters" announce and its ``no_grad`` withholds (F2): each epoch is one
+    ``smaml_adapt_steps_full`` call, one Adam state and one joint gradient clip over both vectors, no
+    per-window feature cache; ``AdaptResult.gcn`` is the adapted flat GCN vector and the validation runs on
+    the adapted base."""
     dev = torch.device(device)
     ctx = ctx or _capi.Context(dims, dev.index or 0)
     ei = edge_index.detach().cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
@@ -125,15 +131,24 @@ def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_
     losses = torch.empty(max(n_train, 1), device=dev)
     ctx.set_task_ids([0])
     ctx.set_dropout(dropout[0], dropout[1], dropout_seed)
-    ctx.adapt_prepare(stream, 1)  # workspace + feature cache before the first epoch (setup, no compute)
+    if train_base:
+        gm, gv = torch.zeros_like(gflat), torch.zeros_like(gflat)
+        res.gcn = gflat
+        ctx.reserve(1, 1)  # the workspace before the first epoch (a trained base has no feature cache)
+    else:
+        ctx.adapt_prepare(stream, 1)  # workspace + feature cache before the first epoch (setup, no compute)
     for _ in range(epochs):
         ctx.set_dropout(dropout[0], dropout[1], dropout_seed)  # masks keyed by the global step index
         ep = len(res.epoch_losses)
         order = np.asarray(orders[ep] if orders is not None else random_sampler_order(n_train).numpy(), np.int32)
         assert order.shape == (n_train,), order.shape
         lr_dev = torch.full((n_train,), lr, device=dev, dtype=torch.float32)
-        ctx.adapt_steps(stream, th, m, v, step, order.reshape(n_train, 1), lr_dev, (0.9, 0.999), 1e-8, wd,
-                        MAX_GRAD_NORM, losses)
+        if train_base:
+            ctx.adapt_steps_full(stream, th, m, v, gflat, gm, gv, step, order.reshape(n_train, 1), lr_dev,
+                                 (0.9, 0.999), 1e-8, wd, MAX_GRAD_NORM, losses)
+        else:
+            ctx.adapt_steps(stream, th, m, v, step, order.reshape(n_train, 1), lr_dev, (0.9, 0.999), 1e-8, wd,
+                            MAX_GRAD_NORM, losses)
         step += n_train
         avg = float(losses[:n_train].double().mean().item())
         res.epoch_losses.append(avg)

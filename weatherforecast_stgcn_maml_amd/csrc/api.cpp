@@ -272,6 +272,16 @@ struct smaml_ctx {
   // [2][R][max(Hc, Cin0)] and the samples' inputs in one piece [R][Cin0], R = nsamples*T*N (grows only)
   HipBuf bg_buf;
   int dx0_fused = 1;  // smaml_set_option("dx0_fused"): k_lstm_dx0 (1) or the GEMM + relu_mask + copies it replaces (0)
+  // smaml_adapt_steps_full (grows only): conv1..conv3's kept outputs [3][R][Hc], two gradient buffers
+  // [2][R][Hc], the t = 0 rows' raw products [B*N][Hc], the samples' inputs [R][Cin0] (B > 1) and the GCN
+  // gradient [Pg], R = B*T*N
+  HipBuf af_buf;
+  int gcn_keep = 1;      // smaml_set_option("gcn_keep"): the forward keeps h1..h3 (1) or the backward recomputes them (0)
+  // smaml_set_option("gcn_dz_fused"): k_gcn_dz (1) or GEMM + gather + mask per layer (0). Off by default: at
+  // config-4 shapes the fused form measured 0.8 % SLOWER per step (1.307 against 1.297 ms, outside both spreads;
+  // profiles/adapt_full_bench.log)
+  int gcn_dz_fused = 0;
+  int64_t af_stats[6] = {};  // smaml_adapt_full_stats: counters of the last smaml_adapt_steps_full call
   const float* gcn = nullptr;
   // workspace
   HipBuf arena;
@@ -855,6 +865,54 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
                            c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
                            rps, d.N, &w.drop));
     src = dst;
+  }
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+// run_gcn for a step whose backward runs through the base (smaml_adapt_steps_full; one task, any B): w.F as
+// run_gcn writes it, and conv1..conv3's outputs (post-ReLU, post-dropout) kept in h[k], per sample
+// [s][T*N][Hc] -- what the GCN backward reads. Fused path: the keep variant of k_gcn_mlp stores the rows
+// t >= 1 from its epilogues, and the t = 0 rows' per-layer launches read and write rows 0 .. N-1 of each
+// sample in h[k] (sample stride T*N rows) instead of ping-ponging through N-row blocks. Per-layer path: layer
+// k writes h[k] directly. Never dedup or compact: every sample keeps its own rows. Same per-row arithmetic as
+// run_gcn. stats: [1] += fused keeping launches, [2] += per-layer keeping launches over all rows.
+int run_gcn_keep(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, float* const h[3], int64_t* stats) {
+  const Dims& d = c->d;
+  Work& w = c->w;
+  w.fcompact = 0;
+  const int rps = d.T * d.N;
+  const int zb = w.Z * w.B;
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
+  if (gcn_mlp_supported(d) && c->kn.gcn_fused) {
+    char* wimg = c->gcn_wimg.as<char>();  // (grown by the caller before its first launch)
+    GcnWOff wo;
+    for (int k = 0; k < 4; ++k) {
+      wo.w[k] = c->go.w[k];
+      wo.b[k] = c->go.b[k];
+    }
+    TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, wimg));  // the base moved in the last step: re-split
+    TIMED(c, s, C_GCN, 2.0 * zb * (d.T - 1) * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+          launch_gcn_mlp(s, d, zb, w.B, xtab_dev, c->gcn, wo, wimg, w.F, &w.drop, false, false, h[0]));
+    stats[1] += 1;
+    for (int k = 0; k < 4; ++k) {  // t = 0 rows: rows 0 .. N-1 of every sample
+      const bool last = k == 3;
+      TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
+            launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, k == 0 ? nullptr : h[k - 1],
+                             last ? w.F : h[k], last, true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k],
+                             d.Hc, ell_c, ell_v, d.N, d.N, &w.drop, rps, rps, rps));
+    }
+    HIP_TRY(hipGetLastError());
+    return SMAML_OK;
+  }
+  for (int k = 0; k < 4; ++k) {
+    const bool last = k == 3;
+    TIMED(c, s, C_GCN, 2.0 * zb * rps * c->go.cin[k] * d.Hc,
+          launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, k == 0 ? nullptr : h[k - 1],
+                           last ? w.F : h[k], last, true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k],
+                           d.Hc, ell_c, ell_v, rps, d.N, &w.drop));
+    stats[2] += 1;
   }
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
@@ -2351,6 +2409,139 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
   return SMAML_OK;
 }
 
+int smaml_adapt_steps_full(smaml_ctx* c, void* stream, float* theta, float* m, float* v, float* gcn, float* gcn_m,
+                           float* gcn_v, int32_t step0, int32_t nsteps, int32_t batch, const int32_t* windows_host,
+                           const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                           float max_norm, float* losses, float* norms) {
+  // (the checks that need no context first: they run without a device too)
+  if (!theta || !m || !v || !gcn || !gcn_m || !gcn_v || !windows_host || !lr_dev || !losses)
+    return fail(SMAML_EINVAL, "smaml_adapt_steps_full: NULL argument");
+  if (nsteps <= 0 || batch <= 0 || step0 < 0)
+    return fail(SMAML_EINVAL, "smaml_adapt_steps_full: nsteps and batch must be positive, step0 non-negative");
+  if (!aligned16(theta) || !aligned16(m) || !aligned16(v) || !aligned16(gcn) || !aligned16(gcn_m) || !aligned16(gcn_v))
+    return fail(SMAML_EINVAL, "smaml_adapt_steps_full: theta, m, v, gcn, gcn_m, gcn_v must be 16-byte aligned");
+  if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  if (!graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_steps_full"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  const Dims& d = c->d;
+  const int B = batch;
+  const int64_t nptr = (int64_t)nsteps * B;
+  std::vector<const float*> ptrs(nptr);
+  for (int64_t i = 0; i < nptr; ++i) {
+    const int wv = windows_host[i];
+    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[0]) return fail(SMAML_EINVAL, "window start out of range");
+    ptrs[i] = c->feats[0] + (int64_t)wv * d.N * d.Cin0;
+  }
+  if ((int64_t)B * d.T * d.N * std::max(d.Hc, 4 * d.H) >= (1ll << 31))
+    return fail(SMAML_EINVAL, "batch too large: B*T*N*max(Hc, 4H) must stay below 2^31");
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  hipStream_t s = (hipStream_t)stream;
+  // every buffer before the first launch; the feature cache (a frozen base's) is neither allocated nor read
+  const int rps = d.T * d.N, R = B * rps;
+  const int64_t hsz = (int64_t)R * d.Hc, tsz = (int64_t)B * d.N * d.Hc, xsz = B > 1 ? (int64_t)R * d.Cin0 : 0;
+  const int64_t Pg = c->go.total, P = c->po.P;
+  const bool fused_gcn = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  TRY(reserve(c, 1, B));
+  if (c->af_buf.grow((5 * hsz + tsz + xsz + Pg) * 4) != hipSuccess ||
+      c->bw_scratch.grow(2 * (int64_t)R * std::max(d.Hc, d.Cin0) * 4) != hipSuccess ||
+      (fused_gcn && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess) ||
+      c->xtab.grow(std::max<int64_t>(nptr, 1024) * (int64_t)sizeof(float*)) != hipSuccess)
+    return fail(SMAML_ENOMEM, "smaml_adapt_steps_full: hipMalloc of the step's buffers failed (nothing was launched)");
+  float* h[3] = {c->af_buf.as<float>(), c->af_buf.as<float>() + hsz, c->af_buf.as<float>() + 2 * hsz};
+  float* g = h[2] + hsz;
+  float* gn = g + hsz;
+  float* top = gn + hsz;
+  float* xcat = top + tsz;
+  float* ggrad = xcat + xsz;
+  // the gradient's pads are zeroed once per call: every step overwrites the tensors and leaves the pads
+  HIP_TRY(hipMemsetAsync(ggrad, 0, (size_t)Pg * 4, s));
+  // the base trains from here on: gcn is the context's GCN parameter vector, cached features are stale
+  c->gcn = gcn;
+  ad_cache_invalidate(c);
+  for (auto& x : c->af_stats) x = 0;
+  const float inv = 1.f / ((float)d.N * d.HfC * B);
+  const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
+  if (dropout) TRY(upload_task_ids(c, s, 1));
+  set_work(c, 1, B);  // (ends a pending smaml_forward / smaml_backward pair)
+  TRY(upload_xtab(c, s, ptrs.data(), nptr));
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
+  const float* Wih0 = theta + c->po.lay[0].wih;
+  for (int k = 0; k < nsteps; ++k) {
+    Work& w = c->w;
+    const float* const* xt = nullptr;
+    TRY(xtab_at(c, (int64_t)k * B, &xt));
+    if (dropout) set_step_drop(c, step0 + k);
+    if (c->gcn_keep) {
+      TRY(run_gcn_keep(c, s, xt, h, c->af_stats));
+    } else {  // A/B: the frozen-base forward, then conv1..conv3 recomputed on the per-layer path (smaml_backward_base)
+      TRY(run_gcn(c, s, xt));
+      for (int l = 0; l < 3; ++l) {
+        TIMED(c, s, C_GCN, 2.0 * R * c->go.cin[l] * d.Hc,
+              launch_gcn_layer(s, d, l, B, B, l == 0 ? xt : nullptr, l == 0 ? nullptr : h[l - 1], h[l], false, true,
+                               c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, ell_c, ell_v, rps, d.N,
+                               &w.drop));
+        c->af_stats[5] += 1;
+      }
+    }
+    w.consec = 0;
+    TRY(run_lstm(c, s, theta, 0));
+    TIMED(c, s, C_HEAD, 2.0 * w.M * d.HfC * d.H, launch_head_loss(s, d, w, theta, 0, c->po, xt, 2.f * inv, true));
+    TRY(run_backward(c, s, theta, 0, c->grad));
+    // dZ4 = dF through conv4's ReLU, per sample: layer 0's dG slab (left by the BPTT) times W_ih0
+    TIMED(c, s, C_MISC, 2.0 * R * 4 * d.H * d.Hc, launch_lstm_dx0(s, d, w, w.dG, Wih0, w.F, g));
+    const float* x0 = ptrs[(int64_t)k * B];  // B = 1: the window is [T*N][Cin0] in the stream already
+    if (B > 1) {
+      for (int si = 0; si < B; ++si)
+        HIP_TRY(hipMemcpyAsync(xcat + (int64_t)si * rps * d.Cin0, ptrs[(int64_t)k * B + si], (size_t)rps * d.Cin0 * 4,
+                               hipMemcpyDeviceToDevice, s));
+      x0 = xcat;
+    }
+    const float sc = w.drop.gcn() ? w.drop.sc_gcn : 1.f;
+    for (int l = 3; l >= 0; --l) {
+      // dW, db of conv l+1 from its pre-activation gradient g and its input
+      TRY(gcn_conv_bwd(c, s, l == 0 ? x0 : h[l - 1], R, rps, c->go.cin[l], gcn + c->go.w[l], d.Hc, g, d.N, nullptr, ggrad,
+                       c->go.w[l], c->go.b[l]));
+      if (l == 0) break;  // (conv1's input gradient: nothing reads it)
+      // through A_hat^T, then the dropout (its mask replayed) and the ReLU after conv l
+      const float* W = gcn + c->go.w[l];
+      if (c->gcn_dz_fused) {
+        TIMED(c, s, C_MISC, 2.0 * R * d.Hc * d.Hc,
+              launch_gcn_dz(s, g, R, d.Hc, W, d.Hc, h[l - 1], sc, rps, d.N, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
+                            c->tr_v.as<float>(), top, gn));
+        c->af_stats[3] += 1;
+      } else {
+        float* t1 = c->bw_scratch.as<float>() + (int64_t)R * std::max(d.Hc, d.Cin0);
+        TIMED(c, s, C_MISC, 2.0 * R * d.Hc * d.Hc, {
+          launch_gemm_nn_plain(s, g, R, d.Hc, W, d.Hc, t1);
+          launch_gather_rows(s, t1, gn, R, d.Hc, d.N, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
+                             c->tr_v.as<float>(), rps);
+          launch_drop_relu_grad(s, gn, h[l - 1], hsz, sc);
+        });
+        c->af_stats[4] += 3;
+      }
+      std::swap(g, gn);
+    }
+    TIMED(c, s, C_MISC, 0,
+          launch_adam_l2_joint(s, theta, c->grad, m, v, P, gcn, ggrad, gcn_m, gcn_v, Pg, c->w.sqpart, lr_dev + k,
+                               step0 + k + 1, beta1, beta2, eps, weight_decay, max_norm, c->w.lpart, c->w.lblocks, inv,
+                               losses + k, norms ? norms + k : nullptr));
+    c->af_stats[0] += 1;
+  }
+  c->w.drop = Drop{};
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+int smaml_adapt_full_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad adapt_full_stats arguments");
+  for (int i = 0; i < 6 && i < cap; ++i) counts[i] = c->af_stats[i];
+  if (count) *count = 6;
+  return SMAML_OK;
+}
+
 int smaml_adapt_prepare_multi(smaml_ctx* c, void* stream, int32_t nregions, const int32_t* tasks_host, int32_t batch) {
   TRY(require_ready(c));
   TRY(check_lstm_dims(c->dims, "smaml_adapt_prepare_multi"));
@@ -2558,6 +2749,10 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->ens_group = (int)value;
   } else if (k == "dx0_fused" && (value == 0 || value == 1)) {
     c->dx0_fused = (int)value;
+  } else if (k == "gcn_keep" && (value == 0 || value == 1)) {
+    c->gcn_keep = (int)value;
+  } else if (k == "gcn_dz_fused" && (value == 0 || value == 1)) {
+    c->gcn_dz_fused = (int)value;
   } else if (k == "adapt_gcn_batch" && value >= 0 && value <= 256) {
     c->ad_gcn_batch = (int)value;
   } else if (k == "wgrad_group_wgs" && value >= 1) {

@@ -382,7 +382,7 @@ const char* products_info();  // product form per GEMM family as built (kernels.
 void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, const float* const* xtab,
                       const float* src, float* dst, bool remap_lstm, bool relu, const float* W,
                       const float* b, int cin, int cout, const int* ell_c, const float* ell_v, int rows_per_sample,
-                      int ell_rows, const Drop* drop = nullptr, int drop_rps = 0);
+                      int ell_rows, const Drop* drop = nullptr, int drop_rps = 0, int src_rps = 0, int dst_rps = 0);
 
 // Exact unsigned division by a run-time invariant d for n < 2^31 (one 64-bit multiply):
 // m = ceil(2^(32+s) / d), s = ceil(log2 d)  =>  n / d == (n * m) >> (32 + s).
@@ -415,6 +415,8 @@ struct GcnMlpArgs {
   GcnWOff wo{};
   const char* wimg = nullptr;          // pre-split W images (launch_gcn_wsplit)
   float* F = nullptr;                  // [Z][T][B*N][Hc]
+  float* h = nullptr;                  // keep variant: conv1..conv3's outputs [3][Z*B][T*N][Hc], else null
+  int64_t hstride = 0;                 // floats between h[k] and h[k + 1]
   int64_t R1 = 0, M = 0;               // rows t >= 1 over all samples; B*N
   FastDiv rows_div{}, b_div{}, n_div{};
   int rows1 = 0, N = 0, T = 0, B = 0, cin0 = 0;
@@ -432,7 +434,7 @@ void launch_gcn_wsplit(hipStream_t s, const Dims& d, const float* gcn, const Gcn
 // time steps) and there is no GCN dropout -- see k_gcn_mlp
 void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* const* xtab, const float* gcn,
                     const GcnWOff& wo, const char* img, float* F, const Drop* drop, bool dedup = false,
-                    bool compact = false);
+                    bool compact = false, float* keep_h = nullptr);
 // out[z] = layer-0 input projection of every distinct stream row of task z's consecutive windows
 // (XgDedup layout) with the gate weights W_ih0 of `params` (theta or the tangent direction U); the
 // weights come from the pre-split images `img` when given (w.gimg.th / .u), else from `params`; F is
@@ -615,6 +617,13 @@ void launch_gemm_nn_plain(hipStream_t s, const float* A, int rows, int K, const 
 // (k_lstm_dx0: the LSTM's layer-0 input gradient through conv4's ReLU; one task, M = w.M = B*N)
 void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* dG0, const float* Wih0, const float* F,
                      float* dZ);
+// The GCN backward's layer-to-layer gradient in one launch (k_gcn_dz) plus one small launch over the t = 0
+// rows (k_gcn_dz_top): out [rows][ncols] = mask_h(A_hat^T (dz [rows][K] . W [K][ncols])), mask_h(x) =
+// h > 0 ? sc x : 0, rows = samples of rps rows whose first N aggregate over the graph (CSR of A_hat^T).
+// top: scratch of (rows / rps) N rows. Bitwise the composed launch_gemm_nn_plain + launch_gather_rows +
+// launch_drop_relu_grad.
+void launch_gcn_dz(hipStream_t s, const float* dz, int rows, int K, const float* W, int ncols, const float* h, float sc,
+                   int rps, int N, const int* csr_p, const int* csr_c, const float* csr_v, float* top, float* out);
 // out[z] = A[z] . W[z]^T (both K-contiguous), Z problems with the given element strides
 void launch_gemm_nt(hipStream_t s, const float* A, int64_t a_zstride, int rows, int K, const float* W,
                     int64_t w_zstride, int ncols, float* out, int64_t o_zstride, int Z);
@@ -628,6 +637,16 @@ void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, i
 void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double* part,
                     const float* lr_dev, int step, float b1, float b2, float eps, float wd, float max_norm,
                     const float* lpart, int lblocks, float inv_count, float* loss);
+
+// launch_adam_l2 over TWO vectors clipped by their joint norm (smaml_adapt_steps_full: the trainable vector
+// p1 [n1] and the GCN vector p2 [n2]): k_sqsum2 writes part [2][SQB] (p1's partials, then p2's), then
+// k_adam_l2_joint takes the clip coefficient from all 2 SQB partials in that order, updates both segments
+// with k_adam_l2's element arithmetic, sums the loss in block 0 and writes the joint norm (before clipping)
+// to norm_out (may be null).
+void launch_adam_l2_joint(hipStream_t s, float* p1, const float* g1, float* m1, float* v1, int64_t n1, float* p2,
+                          const float* g2, float* m2, float* v2, int64_t n2, double* part, const float* lr_dev,
+                          int step, float b1, float b2, float eps, float wd, float max_norm, const float* lpart,
+                          int lblocks, float inv_count, float* loss, float* norm_out);
 
 // launch_adam_l2 for R regions in lockstep (smaml_adapt_steps_multi), region r on blockIdx.y: p, g, m, v
 // [R][n], part [R][SQB], lr_dev [R], lpart [R][lblocks], loss [R]; each region clips by its own norm,

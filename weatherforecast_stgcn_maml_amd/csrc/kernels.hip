@@ -121,14 +121,15 @@ using CfgGcn = GemmCfg<128, 256, 2, 4, true, true, SMAML_GCN_BK, SMAML_X6_GCN>;
 __global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(GcnA la, RowMajorKC lb, const float* __restrict__ bias,
                                                            float* __restrict__ out, int cout, int remap, int relu,
                                                            int T, int N, int B, FastDiv ndiv, FastDiv bdiv, Drop dr,
-                                                           uint32_t dsite, int drps) {
+                                                           uint32_t dsite, int drps, int orps) {
   __shared__ float smem[CfgGcn::SMEM_FLOATS];
   const int m0 = blockIdx.x * CfgGcn::BM, n0 = blockIdx.y * CfgGcn::BN;
   Acc<CfgGcn> acc;
   acc.zero();
   // only tiles that reach a sample's t = 0 block (its first N rows) need the ELL gather
+  // (and tiles of samples that are not one after another in the source: la.sstride)
   const int q0 = m0 - (int)la.rps_div.div((uint32_t)m0) * la.rps;
-  if (q0 < la.ell_rows || q0 + CfgGcn::BM > la.rps) {
+  if (q0 < la.ell_rows || q0 + CfgGcn::BM > la.rps || la.sstride != (int64_t)la.rps * la.cin) {
     gemm_mainloop<CfgGcn, SMAML_IGLP>(la, lb, m0, n0, 0, la.cin, acc, smem);
   } else if (la.buf && la.cin % CfgGcn::BK == 0) {
     // layers 2-4 away from the t = 0 rows: plain row-major operands, branch-free tile loaders
@@ -163,6 +164,9 @@ __global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(GcnA la, RowMajorKC l
         const int z = (int)bdiv.div((uint32_t)g), s = g - z * B;
         const int t = (int)ndiv.div((uint32_t)q), n = q - t * N;
         orow = ((int64_t)z * T + t) * M + (int64_t)s * N + n;
+      } else if (orps != la.rps) {  // sample g's rows start at row g * orps of the destination
+        const int g = (int)la.rps_div.div((uint32_t)row);
+        orow = (int64_t)g * orps + (row - g * la.rps);
       }
       float* o = out + orow * cout;
 #pragma unroll
@@ -180,7 +184,7 @@ __global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(GcnA la, RowMajorKC l
 void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, const float* const* xtab,
                       const float* src, float* dst, bool remap_lstm, bool relu, const float* W,
                       const float* b, int cin, int cout, const int* ell_c, const float* ell_v,
-                      int rows_per_sample, int ell_rows, const Drop* drop, int drop_rps) {
+                      int rows_per_sample, int ell_rows, const Drop* drop, int drop_rps, int src_rps, int dst_rps) {
   // train-mode dropout after the ReLU of conv1..conv3 (hybrid_model.py:67,70,73)
   Drop dr{};
   uint32_t dsite = 0;
@@ -191,7 +195,9 @@ void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, co
   GcnA la;
   la.tab = xtab;
   la.buf = src;
-  la.sstride = (int64_t)rows_per_sample * cin;
+  // src_rps / dst_rps > 0: sample g's rows_per_sample rows start at row g * src_rps of src (layers 2-4) and at
+  // row g * dst_rps of dst (no remap): the t = 0 blocks of T*N-row samples (smaml_adapt_steps_full)
+  la.sstride = (int64_t)(src_rps > 0 ? src_rps : rows_per_sample) * cin;
   la.ec = ell_c;
   la.ev = ell_v;
   la.rps_div = FastDiv((uint32_t)rows_per_sample);
@@ -203,7 +209,8 @@ void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, co
   dim3 grid((la.R + CfgGcn::BM - 1) / CfgGcn::BM, (cout + CfgGcn::BN - 1) / CfgGcn::BN);
   k_gcn_layer<<<grid, CfgGcn::NTH, 0, s>>>(la, lb, b, dst, cout, remap_lstm ? 1 : 0, relu ? 1 : 0, d.T, d.N, B,
                                            FastDiv((uint32_t)d.N), FastDiv((uint32_t)B), dr, dsite,
-                                           drop_rps > 0 ? drop_rps : rows_per_sample);
+                                           drop_rps > 0 ? drop_rps : rows_per_sample,
+                                           dst_rps > 0 ? dst_rps : rows_per_sample);
 }
 
 // ====================================================================================
@@ -2843,6 +2850,79 @@ void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* d
                                          FastDiv((uint32_t)d.N));
 }
 
+// The GCN backward's gradient from conv k+1's pre-activation to conv k's (smaml_adapt_steps_full), one GEMM
+// launch instead of launch_gemm_nn_plain + k_gather_rows + k_drop_relu_grad over all rows:
+//   out[r] = mask(A_hat^T (dz . W))[r],  mask(x) = h > 0 ? sc x : 0   (h = conv k's output, post-dropout)
+// The rows q = r mod rps >= N of a sample see only their self loop (F3), so A_hat^T is the identity there and
+// the epilogue masks the product and stores it. The rows q < N aggregate over the graph: their raw product goes
+// to `top` [(rows / rps) N][ncols], and k_gcn_dz_top gathers (k_gather_rows's CSR sum, term for term) and
+// masks them. k_gemm_nn's tile and K order and the two kernels' expressions: bitwise the composed form.
+__global__ __launch_bounds__(NT) void k_gcn_dz(const float* __restrict__ dz, const float* __restrict__ W,
+                                               const float* __restrict__ h, float* __restrict__ out,
+                                               float* __restrict__ top, int rows, int K, int ncols, int rps, int N,
+                                               float sc, FastDiv rdiv) {
+  __shared__ float smem[CfgNN::SMEM_FLOATS];
+  RowMajorKC la{dz, rows, K};
+  RowMajorMC lb{W, K, ncols};
+  const int m0 = blockIdx.x * CfgNN::BM, n0 = blockIdx.y * CfgNN::BN;
+  Acc<CfgNN> acc;
+  acc.zero();
+  gemm_mainloop<CfgNN>(la, lb, m0, n0, 0, K, acc, smem);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = m0 + acc_row<CfgNN>(0, r);
+    if (m >= rows) continue;
+    const int g = (int)rdiv.div((uint32_t)m), q = m - g * rps;
+    if (q < N) {
+      float* o = top + ((int64_t)g * N + q) * ncols;
+#pragma unroll
+      for (int j = 0; j < CfgNN::WTN; ++j) {
+        const int c = n0 + acc_col<CfgNN>(j);
+        if (c < ncols) o[c] = acc.v[0][j][r];
+      }
+    } else {
+      const float* hh = h + (int64_t)m * ncols;
+      float* o = out + (int64_t)m * ncols;
+#pragma unroll
+      for (int j = 0; j < CfgNN::WTN; ++j) {
+        const int c = n0 + acc_col<CfgNN>(j);
+        if (c < ncols) o[c] = hh[c] > 0.f ? sc * acc.v[0][j][r] : 0.f;
+      }
+    }
+  }
+}
+
+// out[g rps + q] = mask(sum_e csr_v[e] top[g N + csr_c[e]]) for q < N: one float4 of one row per thread
+__global__ void k_gcn_dz_top(const float* __restrict__ top, const float* __restrict__ h, float* __restrict__ out,
+                             int nrows, int cols, int rps, int N, float sc, const int* __restrict__ csr_p,
+                             const int* __restrict__ csr_c, const float* __restrict__ csr_v) {
+  const int q4 = cols / 4;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)nrows * q4) return;
+  const int r = (int)(i / q4), k = 4 * (int)(i - (int64_t)r * q4);
+  const int g = r / N, q = r - g * N;
+  const float* sb = top + (int64_t)g * N * cols;
+  float4 v = f4zero();
+  for (int e = csr_p[q]; e < csr_p[q + 1]; ++e) v = fma4(csr_v[e], ld4(sb + (int64_t)csr_c[e] * cols + k), v);
+  const int64_t o = ((int64_t)g * rps + q) * cols + k;
+  const float4 hv = ld4(h + o);
+  v.x = hv.x > 0.f ? sc * v.x : 0.f;
+  v.y = hv.y > 0.f ? sc * v.y : 0.f;
+  v.z = hv.z > 0.f ? sc * v.z : 0.f;
+  v.w = hv.w > 0.f ? sc * v.w : 0.f;
+  st4(out + o, v);
+}
+
+void launch_gcn_dz(hipStream_t s, const float* dz, int rows, int K, const float* W, int ncols, const float* h, float sc,
+                   int rps, int N, const int* csr_p, const int* csr_c, const float* csr_v, float* top, float* out) {
+  static_assert(CfgNN::WTM == 1, "k_gcn_dz's epilogue walks one 32-row tile per wave");
+  dim3 grid((rows + CfgNN::BM - 1) / CfgNN::BM, (ncols + CfgNN::BN - 1) / CfgNN::BN, 1);
+  k_gcn_dz<<<grid, CfgNN::NTH, 0, s>>>(dz, W, h, out, top, rows, K, ncols, rps, N, sc, FastDiv((uint32_t)rps));
+  const int nrows = rows / rps * N;
+  const int64_t n = (int64_t)nrows * (ncols / 4);
+  k_gcn_dz_top<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(top, h, out, nrows, ncols, rps, N, sc, csr_p, csr_c, csr_v);
+}
+
 // out[z] = A[z] . W[z]^T, both operands K-contiguous ([rows][K], [ncols][K]); the batch-1 forward's
 // hoisted layer-0 input projection (XG[t*M + m][n] = F[t][m] . W_ih0[n] for all T steps in one
 // throughput-bound launch instead of inside every latency-bound wavefront diagonal).
@@ -3089,6 +3169,84 @@ void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v,
   const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
   k_adam_l2<<<nb, NT, 0, s>>>(p, g, m, v, n, part, lr_dev, bc1, (float)std::sqrt(bc2), b1, b2, eps, wd, max_norm,
                               lpart, lblocks, inv_count, loss);
+}
+
+// Whole-model adaptation step (smaml_adapt_steps_full): clip_grad_norm_ over the gradients of TWO vectors
+// jointly, then Adam on both. k_sqsum2: k_sqsum's partials of vector 1 (blockIdx.y = 0) into part[0 .. SQB)
+// and of vector 2 (blockIdx.y = 1) into part[SQB .. 2 SQB) in one launch.
+__global__ void k_sqsum2(const float* __restrict__ g1, int64_t n1, const float* __restrict__ g2, int64_t n2,
+                         double* __restrict__ part) {
+  __shared__ double red[NT / 64];
+  const int z = blockIdx.y;
+  const float* gz = z == 0 ? g1 : g2;
+  const int64_t P = z == 0 ? n1 : n2;
+  const int64_t per = (P + SQB - 1) / SQB;
+  const int64_t b = (int64_t)blockIdx.x * per, e = b + per < P ? b + per : P;
+  double acc = 0.0;
+#pragma unroll 8
+  for (int64_t i = b + threadIdx.x; i < e; i += NT) {
+    const double v = gz[i];
+    acc += v * v;
+  }
+  const double s = block_sum_d(acc, red);
+  if (threadIdx.x == 0) part[(int64_t)z * SQB + blockIdx.x] = s;
+}
+
+// k_adam_l2 on both vectors (segment = blockIdx.y) with the clip coefficient of the joint norm: the sum of
+// all 2 SQB partials in order (vector 1's, then vector 2's). Block (0, 0) sums the loss as k_adam_l2 does and
+// writes the joint norm before clipping. The element arithmetic is k_adam_l2's, expression for expression.
+__global__ void k_adam_l2_joint(float* __restrict__ p1, const float* __restrict__ g1, float* __restrict__ m1,
+                                float* __restrict__ v1, int64_t n1, float* __restrict__ p2,
+                                const float* __restrict__ g2, float* __restrict__ m2, float* __restrict__ v2,
+                                int64_t n2, const double* __restrict__ part, const float* __restrict__ lr_dev,
+                                double bc1, float bc2_sqrt, float b1, float b2, float eps, float wd, float max_norm,
+                                const float* __restrict__ lpart, int lblocks, float inv_count,
+                                float* __restrict__ loss, float* __restrict__ norm_out) {
+  const bool first = blockIdx.x == 0 && blockIdx.y == 0;
+  if (loss && first) {
+    __shared__ float red[NT / 64];
+    float a = 0.f;
+    for (int i = threadIdx.x; i < lblocks; i += NT) a += lpart[i];
+    const float s = block_sum(a, red);
+    if (threadIdx.x == 0) *loss = s * inv_count;
+  }
+  double t = 0.0;
+  for (int i = 0; i < 2 * SQB; ++i) t += part[i];
+  const float total = (float)sqrt(t);
+  if (norm_out && first && threadIdx.x == 0) *norm_out = total;
+  float coef = max_norm / (total + 1e-6f);
+  coef = coef < 1.f ? coef : 1.f;
+  const bool seg2 = blockIdx.y != 0;
+  float* __restrict__ p = seg2 ? p2 : p1;
+  const float* __restrict__ g = seg2 ? g2 : g1;
+  float* __restrict__ m = seg2 ? m2 : m1;
+  float* __restrict__ v = seg2 ? v2 : v1;
+  const int64_t n = seg2 ? n2 : n1;
+  const float lr = *lr_dev;
+  const float step_size = (float)((double)lr / bc1);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float gi = fmaf(wd, p[i], g[i] * coef);
+    const float mi = m[i] + (1.f - b1) * (gi - m[i]);
+    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    p[i] = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+// (two launches, as launch_adam_l2: see the measurement above it)
+void launch_adam_l2_joint(hipStream_t s, float* p1, const float* g1, float* m1, float* v1, int64_t n1, float* p2,
+                          const float* g2, float* m2, float* v2, int64_t n2, double* part, const float* lr_dev,
+                          int step, float b1, float b2, float eps, float wd, float max_norm, const float* lpart,
+                          int lblocks, float inv_count, float* loss, float* norm_out) {
+  const int64_t nmax = n1 > n2 ? n1 : n2;
+  int nb = (int)((nmax + NT - 1) / NT);
+  if (nb > 2048) nb = 2048;
+  k_sqsum2<<<dim3(SQB, 2), NT, 0, s>>>(g1, n1, g2, n2, part);
+  const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
+  k_adam_l2_joint<<<dim3(nb, 2), NT, 0, s>>>(p1, g1, m1, v1, n1, p2, g2, m2, v2, n2, part, lr_dev, bc1,
+                                             (float)std::sqrt(bc2), b1, b2, eps, wd, max_norm, lpart, lblocks,
+                                             inv_count, loss, norm_out);
 }
 
 // k_adam_l2 for R regions adapted in lockstep, region r = blockIdx.y: its own parameter / moment / gradient

@@ -87,7 +87,11 @@ __global__ void k_gcn_wsplit(const float* __restrict__ gcn, GcnWOff wo, int HC, 
 typedef __attribute__((address_space(3))) void gm_lds_t;
 typedef __attribute__((address_space(1))) const void gm_gbl_t;
 
-template <int HC>
+// KEEP (smaml_adapt_steps_full, whose backward runs through the base): the epilogues of conv1..conv3 also
+// store their outputs (post-ReLU, post-dropout: the next layer's operand) to a.h[layer], per sample
+// [g][T*N][HC] at row q -- the layout the GCN backward reads -- with the F store's float4-per-lane pattern.
+// Never with dedup (every sample keeps its own rows). The arithmetic, and so F, is the plain kernel's.
+template <int HC, bool KEEP = false>
 __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
   constexpr int NT = HC / 32;  // channel tiles
   constexpr int SB = gm_step_bytes(HC);
@@ -117,6 +121,8 @@ __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
   if (a.compact) {  // once, at compact row M + (t - 1) N + n (t = the stream row here): tt = t_lo only
     frow = a.F + (((int64_t)z * a.T) * a.M + a.M + (int64_t)(t - 1) * a.N + n) * HC;
   }
+  float* hrow = nullptr;  // KEEP: this lane's row of h[0]
+  if constexpr (KEEP) hrow = a.h + ((int64_t)g * (a.T * a.N) + q) * HC;
   uint64_t didx = 0;
   if (a.dr.gcn()) didx = (((uint64_t)a.dr.task_id[z] * a.B + s) * (uint64_t)(a.T * a.N) + (uint64_t)q) * HC;
 
@@ -191,6 +197,11 @@ __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
           if (drop) x = drop_keep(dsite, didx + p0 + e, a.dr.thr_gcn) ? x * a.dr.sc_gcn : 0.f;
           act[ci][4 * gq + e] = x;
           acc[ci][4 * gq + e] = 0.f;
+        }
+        if constexpr (KEEP) {
+          if (layer < 3 && valid)
+            st4(hrow + (int64_t)layer * a.hstride + p0,
+                make_float4(act[ci][4 * gq], act[ci][4 * gq + 1], act[ci][4 * gq + 2], act[ci][4 * gq + 3]));
         }
       }
   };
@@ -273,8 +284,12 @@ void launch_gcn_expand(hipStream_t s, const Dims& d, int Z, int B, const float* 
 bool gcn_mlp_supported(const Dims& d) { return d.Hc == 256 && d.Cin0 <= 32 && d.Cin0 % 4 == 0 && d.T > 1; }
 
 void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* const* xtab, const float* gcn,
-                    const GcnWOff& wo, const char* img, float* F, const Drop* drop, bool dedup, bool compact) {
+                    const GcnWOff& wo, const char* img, float* F, const Drop* drop, bool dedup, bool compact,
+                    float* keep_h) {
   GcnMlpArgs a{};
+  if (keep_h) dedup = false;
+  a.h = keep_h;
+  a.hstride = (int64_t)Zb * d.T * d.N * d.Hc;
   a.xtab = xtab;
   a.gcn = gcn;
   a.wo = wo;
@@ -294,7 +309,10 @@ void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* co
   a.cin0 = d.Cin0;
   if (drop && drop->gcn()) a.dr = *drop;
   const unsigned blocks = (unsigned)((a.R1 + GM_ROWS - 1) / GM_ROWS);
-  k_gcn_mlp<256><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
+  if (keep_h)
+    k_gcn_mlp<256, true><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
+  else
+    k_gcn_mlp<256><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
 }
 
 }  // namespace smaml
