@@ -295,7 +295,8 @@ int smaml_adapt_steps_multi(smaml_ctx* ctx, void* stream, int32_t nregions, cons
 int smaml_adapt_prepare_multi(smaml_ctx* ctx, void* stream, int32_t nregions, const int32_t* tasks_host,
                               int32_t batch);
 
-/* Host-timed phases of the last smaml_adapt_steps call, in ms: [0] workspace reserve, [1] feature-
+/* Host-timed phases of the last smaml_adapt_steps / smaml_adapt_steps_multi / smaml_adapt_steps_full call (the
+ * last never fills a cache: [0] .. [2] stay 0 there), in ms: [0] workspace reserve, [1] feature-
  * cache allocation, [2] the batched feature-cache fill, [3] the step loop ([2] and [3] are enqueue
  * times unless smaml_set_option("adapt_phase_sync", 1), which ends each with a stream sync).
  * Writes min(cap, count) entries; *count = number of phases; *filled = windows whose features a
@@ -320,8 +321,8 @@ int smaml_adapt_phases(const smaml_ctx* ctx, double* ms, int32_t cap, int32_t* c
  * pair is consumed. The forward keeps conv1..conv3's outputs for the backward (k_gcn_mlp's keep variant where
  * the fused GCN runs, else the per-layer launches write them in place), the layer-to-layer gradient is a GEMM,
  * a gather and a mask pass per layer (option "gcn_dz_fused" = 1: one GEMM with the mask in its epilogue plus a
- * gather over the t = 0 rows, k_gcn_dz), and the clip and Adam of both vectors are two launches (k_sqsum2,
- * k_adam_l2_joint). Option "gcn_keep" = 0 recomputes the kept outputs instead. The kept activations and gradient buffers (batch*T*N rows x 5 Hc floats and smaller
+ * gather over the t = 0 rows, k_gcn_dz), and the clip and Adam of both vectors are two launches (k_sqsum,
+ * k_adam_l2 over two segments). Option "gcn_keep" = 0 recomputes the kept outputs instead. The kept activations and gradient buffers (batch*T*N rows x 5 Hc floats and smaller
  * pieces) are the context's own: they grow only and are freed by smaml_destroy.
  * Checked before anything is allocated or launched, the NULL arguments, alignment and counts before a device
  * is needed: NULL arguments (norms may be NULL), alignment, nsteps and batch positive, step0 non-negative
@@ -529,7 +530,7 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  with k_gcn_dz, one GEMM with the mask in its epilogue plus a gather over
  *                                  the t = 0 rows (1; bitwise equal; measured 0.8 % slower per step at
  *                                  config-4 shapes, so it ships off);
- *   "adapt_phase_sync":            smaml_adapt_steps synchronises its stream after the feature-cache fill
+ *   "adapt_phase_sync":            smaml_adapt_steps (and _multi, _full) synchronises its stream after the feature-cache fill
  *                                  and after the step loop so smaml_adapt_phases reports GPU time (0,
  *                                  the default; measurement only);
  *   "gcn_dedup":                   smaml_meta_step steps whose every task reads B consecutive windows

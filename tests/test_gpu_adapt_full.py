@@ -286,6 +286,27 @@ def test_first_loss_is_the_frozen_step_s_and_the_cache_follows_the_base(name):
     assert abs(float(loss[0]) - want) < 1e-5 * want, (float(loss[0]), want)
 
 
+@pytest.mark.parametrize("name", ["cfg1", "hc256_t3"])
+def test_two_segment_update_is_bitwise_the_one_segment_update(name):
+    """With max_norm = 1e30 the clip coefficient is exactly 1 whether the norm is the trainable vector's or the
+    joint one, so one step from equal starts on the same window leaves theta, m and v bitwise equal: the R = 1,
+    S = 2 clip + Adam launch (smaml_adapt_steps_full) against the R = 1, S = 1 launch (smaml_adapt_steps). The
+    base itself has moved."""
+    r, f = Run(name), Run(name)
+    r.max_norm = 1e30
+    r.full(windows=r.windows[:1])
+    f.ctx.set_gcn_params(f.gcn)
+    loss = torch.empty(1, device=DEV)
+    f.ctx.adapt_steps(f.st, f.theta, f.m, f.v, STEP0, f.windows[:1], f.lr_dev, (0.9, 0.999), 1e-8, WD, 1e30, loss)
+    torch.cuda.synchronize()
+    assert torch.equal(loss[0], r.losses[0])
+    for a, b in ((r.theta, f.theta), (r.m, f.m), (r.v, f.v)):
+        assert torch.equal(a, b)
+    assert float(r.m.abs().sum()) > 0.0  # the step did run
+    assert not torch.equal(r.gcn, f.gcn)
+    assert float(f.gm.abs().sum()) == 0.0 and float(r.gm.abs().sum()) > 0.0
+
+
 def test_workspace_is_not_grown_and_errors_leave_the_vectors():
     name = "hc48_b3"
     r = Run(name)

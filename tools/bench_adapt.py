@@ -31,7 +31,7 @@ process, each repetition --steps steps timed on the host around a device synchro
                       costs on top of it, not a race
 Medians of --reps repetitions after --warmup, with min and max; then the event time per timing category of one
 more repetition of each library arm (gcn_layer: the GCN forward and recompute; misc: k_lstm_dx0, k_gcn_dz or its
-composed form, the weight re-split, k_sqsum2 + k_adam_l2_joint). The lines go to stdout and to --log
+composed form, the weight re-split, k_sqsum + k_adam_l2). The lines go to stdout and to --log
 (default profiles/adapt_full_bench.log); ONE JSON line last.
 """
 from __future__ import annotations

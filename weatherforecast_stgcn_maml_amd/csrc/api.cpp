@@ -1623,6 +1623,41 @@ int gcn_conv_bwd(smaml_ctx* c, hipStream_t s, const float* x, int rows, int rps,
   return SMAML_OK;
 }
 
+// The GCN backward, conv4 -> conv1, over `rows` rows (samples of rps rows) from dZ4 in g (smaml_backward_base and
+// the step that trains the base). Per layer l: dW, db of conv l+1 into grad at the layer's offsets (grad null:
+// none), then -- unless it is conv1 and its input gradient is not wanted -- dz . W, the A_hat^T gather, the mask
+// of the dropout (replayed) and the ReLU after conv l (its kept output h[l-1]; conv1's input has none), and
+// g <-> gn. x0: conv1's input [rows][Cin0]. dz_top: k_gcn_dz's scratch, which selects the one-launch form of
+// the layer-to-layer gradient (null: GEMM + gather + mask; bitwise the same). stats (optional): [3] += k_gcn_dz
+// launches, [4] += launches of the composed form. cat: the timing category of the layer-to-layer launches. On
+// return g holds the last gradient written (conv1's input gradient [rows][Cin0] when want_dx0).
+int gcn_backward_chain(smaml_ctx* c, hipStream_t s, const float* x0, float* const h[3], float*& g, float*& gn, int rows,
+                       int rps, const float* gcn, float* grad, bool want_dx0, float* dz_top, int64_t* stats, int cat) {
+  const Dims& d = c->d;
+  const float sc = c->w.drop.gcn() ? c->w.drop.sc_gcn : 1.f;
+  for (int l = 3; l >= 0; --l) {
+    const float* x = l == 0 ? x0 : h[l - 1];
+    const float* W = gcn + c->go.w[l];
+    const int cin = c->go.cin[l];
+    if (grad) TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, d.N, nullptr, grad, c->go.w[l], c->go.b[l]));
+    if (l == 0 && !want_dx0) break;
+    if (l > 0 && dz_top) {
+      TIMED(c, s, cat, 2.0 * rows * d.Hc * cin,
+            launch_gcn_dz(s, g, rows, d.Hc, W, cin, h[l - 1], sc, rps, d.N, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
+                          c->tr_v.as<float>(), dz_top, gn));
+      if (stats) stats[3] += 1;
+    } else {
+      TIMED(c, s, cat, 2.0 * rows * d.Hc * cin, {
+        TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, d.N, gn, nullptr, 0, 0));
+        if (l > 0) launch_drop_relu_grad(s, gn, h[l - 1], (int64_t)rows * d.Hc, sc);
+      });
+      if (stats) stats[4] += l > 0 ? 3 : 2;
+    }
+    std::swap(g, gn);
+  }
+  return SMAML_OK;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -2224,7 +2259,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
 // cache slots. Per-row GCN arithmetic does not depend on how many samples a launch holds, so the
 // features are bitwise those of the per-step fill (the first epoch no longer runs 960 batch-1 GCNs).
 // The windows are those of task `task` (its stream, its cache), windows[i * stride] for i < n.
-static int ad_cache_fill(smaml_ctx* c, hipStream_t s, int task, const int32_t* windows, int64_t n, int64_t stride = 1) {
+static int ad_cache_fill(smaml_ctx* c, hipStream_t s, int task, const int32_t* windows, int64_t n, int64_t stride) {
   const Dims& d = c->d;
   const int64_t fsz = (int64_t)d.T * d.N * d.Hc;
   smaml_ctx::AdCache& ac = c->ad[task];
@@ -2337,67 +2372,206 @@ int smaml_adapt_prepare(smaml_ctx* c, void* stream, int32_t batch) {
   return ad_prepare(c, (hipStream_t)stream, batch, &task0, 1, &cache);
 }
 
-int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float* v, int32_t step0, int32_t nsteps,
-                      int32_t batch, const int32_t* windows_host, const float* lr_dev, float beta1, float beta2,
-                      float eps, float weight_decay, float max_norm, float* losses) {
-  using clk = std::chrono::steady_clock;
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_adapt_steps"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  if (!theta || !m || !v || nsteps <= 0 || batch <= 0 || !windows_host || !lr_dev || !losses || step0 < 0)
-    return fail(SMAML_EINVAL, "bad adapt_steps arguments");
-  TRY(ensure_device(c));
-  hipStream_t s = (hipStream_t)stream;
+// One call's adaptation steps: R regions (tasks of smaml_set_tasks) stepped in lockstep, every per-region array
+// at the region's index -- theta / m / v [R][P], windows [nsteps][R][B], lr_dev and losses [nsteps][R], wd [R].
+// gcn / gcn_m / gcn_v set: the GCN base trains too (one region; norms [nsteps] optional); null: a frozen base.
+struct AdaptCall {
+  const int32_t* tasks;
+  int R;
+  float *theta, *m, *v;
+  float *gcn, *gcn_m, *gcn_v;
+  int step0, nsteps, B;
+  const int32_t* windows;
+  const float* lr_dev;
+  const float* wd;  // host
+  float beta1, beta2, eps, max_norm;
+  float* losses;
+  float* norms;
+  bool name_regions;  // window errors name the region, task and step (the lockstep entry point's wording)
+};
+
+// The buffers of a step that trains the base (af_buf): conv1..conv3's kept outputs, the GCN backward's two
+// gradient buffers, k_gcn_dz's scratch, the step's windows side by side (B > 1) and the GCN gradient.
+struct AfBufs {
+  float* h[3];
+  float *g, *gn, *top, *xcat, *ggrad;
+};
+
+// Every buffer of a base-training call before its first launch (a failure leaves the caller's vectors
+// untouched); the feature cache (a frozen base's) is neither allocated nor read. From here on the base trains:
+// gcn is the context's GCN parameter vector and cached features are stale.
+static int af_prepare(smaml_ctx* c, hipStream_t s, const AdaptCall& a, int64_t nptr, AfBufs* f) {
   const Dims& d = c->d;
-  const int B = batch;
-  const int64_t nptr = (int64_t)nsteps * B;
-  std::vector<const float*> ptrs(nptr);
-  for (int64_t i = 0; i < nptr; ++i) {
-    const int wv = windows_host[i];
-    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[0]) return fail(SMAML_EINVAL, "window start out of range");
-    ptrs[i] = c->feats[0] + (int64_t)wv * d.N * d.Cin0;
+  const int B = a.B, rows = B * d.T * d.N;
+  const int64_t hsz = (int64_t)rows * d.Hc, tsz = (int64_t)B * d.N * d.Hc, xsz = B > 1 ? (int64_t)rows * d.Cin0 : 0;
+  const int64_t Pg = c->go.total;
+  const bool fused_gcn = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  TRY(reserve(c, 1, B));
+  if (c->af_buf.grow((5 * hsz + tsz + xsz + Pg) * 4) != hipSuccess ||
+      c->bw_scratch.grow(2 * (int64_t)rows * std::max(d.Hc, d.Cin0) * 4) != hipSuccess ||
+      (fused_gcn && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess) ||
+      c->xtab.grow(std::max<int64_t>(nptr, 1024) * (int64_t)sizeof(float*)) != hipSuccess)
+    return fail(SMAML_ENOMEM, "smaml_adapt_steps_full: hipMalloc of the step's buffers failed (nothing was launched)");
+  float* p = c->af_buf.as<float>();
+  for (int l = 0; l < 3; ++l) f->h[l] = p + l * hsz;
+  f->g = p + 3 * hsz;
+  f->gn = f->g + hsz;
+  f->top = f->gn + hsz;
+  f->xcat = f->top + tsz;
+  f->ggrad = f->xcat + xsz;
+  // the gradient's pads are zeroed once per call: every step overwrites the tensors and leaves the pads
+  HIP_TRY(hipMemsetAsync(f->ggrad, 0, (size_t)Pg * 4, s));
+  c->gcn = a.gcn;
+  ad_cache_invalidate(c);
+  for (auto& x : c->af_stats) x = 0;
+  return SMAML_OK;
+}
+
+// The adaptation step, once: nsteps steps of the call's regions, in launch sets of ad_group_size regions (Z = a
+// set's regions on the task axis, per-task parameters at stride P; one region: stride 0). Per set and step:
+// features -> LSTM -> head + loss -> backward (-> the GCN backward, base trained) -> clip + Adam. The features
+// come from the cache slot itself (Z = 1), from the set's Z slots gathered into the workspace's F by one copy
+// launch (k_gather_slabs, slot pointers uploaded with the window table), from the frozen forward (no cache: B > 1
+// or GCN dropout), or from the keeping forward of a trained base. Cache fill: up front in batched GCN passes
+// (adapt_gcn_batch > 1, or several regions); else the single region's window on its first use, counted in
+// ad_ph.filled.
+static int adapt_run(smaml_ctx* c, hipStream_t s, const AdaptCall& a) {
+  using clk = std::chrono::steady_clock;
+  const Dims& d = c->d;
+  const int B = a.B, R = a.R, nsteps = a.nsteps;
+  const bool train = a.gcn != nullptr;
+  if (train && R != 1) return fail(SMAML_EINVAL, "internal: adapt_run trains the base of one region only");
+  // one table for the call: the window pointers [nsteps][R][B], then (cache) the slot pointers [nsteps][R]
+  const int64_t nwin = (int64_t)nsteps * R * B, nslot = (int64_t)nsteps * R;
+  std::vector<const float*> ptrs(nwin);
+  for (int64_t i = 0; i < nwin; ++i) {
+    const int r = (int)(i / B % R), task = a.tasks[r];
+    const int wv = a.windows[i];
+    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[task]) {
+      if (!a.name_regions) return fail(SMAML_EINVAL, "window start out of range");
+      return fail(SMAML_EINVAL, "adapt_steps_multi: region " + std::to_string(r) + " (task " + std::to_string(task) +
+                                    "): window " + std::to_string(wv) + " of step " + std::to_string(i / B / R) +
+                                    " out of range (stream of " + std::to_string(c->t_total[task]) + " rows)");
+    }
+    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
   }
+  if (train && (int64_t)B * d.T * d.N * std::max(d.Hc, 4 * d.H) >= (1ll << 31))
+    return fail(SMAML_EINVAL, "batch too large: B*T*N*max(Hc, 4H) must stay below 2^31");
+  TRY(ensure_device(c));
   c->ad_ph = AdPhases{};
   bool cache = false;
-  const int32_t task0 = 0;
-  TRY(ad_prepare(c, s, B, &task0, 1, &cache));  // no allocation after smaml_adapt_prepare / an earlier call
-  const bool fill_batched = B == 1 && !(c->p_gcn > 0.f) && c->ad_gcn_batch > 1;
-  const int64_t P = c->po.P;
+  AfBufs f{};
+  if (train) {
+    TRY(check_device_error(c));
+    TRY(af_prepare(c, s, a, nwin, &f));
+  } else {
+    TRY(ad_prepare(c, s, B, a.tasks, R, &cache));  // no allocation after smaml_adapt_prepare[_multi] / an earlier call
+  }
+  const int G = ad_group_size(c, R);  // regions per launch set
+  const int64_t P = c->po.P, Pg = c->go.total;
+  const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
+  const int rows = B * d.T * d.N;
   const float inv = 1.f / ((float)d.N * d.HfC * B);
   const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
-  if (dropout) TRY(upload_task_ids(c, s, 1));
-  // Batch-1 steps without GCN dropout reuse each window's GCN features across epochs (F2).
-  const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
+  if (dropout) {  // masks keyed by each region's task id (smaml_set_task_ids; default: the task index)
+    std::vector<int32_t> ids(R);
+    for (int r = 0; r < R; ++r) ids[r] = a.tasks[r] < (int)c->task_ids.size() ? c->task_ids[a.tasks[r]] : a.tasks[r];
+    TRY(c->stage.upload(s, c->task_id_dev, ids.data(), (int64_t)R * 4));
+  }
+  // Batch-1 steps without GCN dropout reuse each window's GCN features across epochs (F2; cache implies B = 1).
   auto t0 = clk::now();
-  if (cache && fill_batched) {
-    TRY(ad_cache_fill(c, s, 0, windows_host, nsteps));
-    if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
+  if (cache) {
+    if (c->ad_gcn_batch > 1 || R > 1) {  // every region's missing windows up front, region by region
+      for (int r = 0; r < R; ++r) TRY(ad_cache_fill(c, s, a.tasks[r], a.windows + r, nsteps, R));
+      if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
+    }
+    ptrs.resize(nwin + nslot);
+    for (int64_t i = 0; i < nslot; ++i)
+      ptrs[nwin + i] = c->ad[a.tasks[i % R]].F.as<float>() + (int64_t)a.windows[i] * fsz;
   }
   auto t1 = clk::now();
-  set_work(c, 1, B);
-  TRY(upload_xtab(c, s, ptrs.data(), nptr));
+  TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
   for (int k = 0; k < nsteps; ++k) {
-    const float* const* xt = nullptr;
-    TRY(xtab_at(c, (int64_t)k * B, &xt));
-    if (dropout) set_step_drop(c, step0 + k);
-    if (cache) {
-      const int wv = windows_host[k];
-      c->w.F = c->ad[0].F.as<float>() + (int64_t)wv * fsz;
-      if (!c->ad[0].valid[wv]) {
-        TRY(run_gcn(c, s, xt));  // writes the window's features straight into its cache slot
-        c->ad[0].valid[wv] = 1;
-        c->ad_ph.filled += 1;
+    for (int r0 = 0; r0 < R; r0 += G) {
+      const int Z = std::min(G, R - r0);
+      set_work(c, Z, B);  // (ends a pending smaml_forward / smaml_backward pair)
+      Work& w = c->w;
+      // (one region: the parameters at stride 0)
+      float* th = a.theta + (int64_t)r0 * P;
+      const int64_t ts = Z > 1 ? P : 0;
+      const int64_t at = (int64_t)k * R + r0;  // the set's first region in the per-step arrays
+      const float* const* xt = nullptr;
+      TRY(xtab_at(c, at * B, &xt));
+      if (dropout) {
+        set_step_drop(c, a.step0 + k);
+        w.drop.task_id = c->task_id_dev + r0;
       }
-      TRY(run_lstm(c, s, theta, 0));
-    } else {
-      TRY(run_forward(c, s, theta, 0, xt));
+      if (train) {
+        if (c->gcn_keep) {
+          TRY(run_gcn_keep(c, s, xt, f.h, c->af_stats));
+        } else {  // A/B: the frozen-base forward, then conv1..conv3 recomputed on the per-layer path (smaml_backward_base)
+          TRY(run_gcn(c, s, xt));
+          for (int l = 0; l < 3; ++l) {
+            TIMED(c, s, C_GCN, 2.0 * rows * c->go.cin[l] * d.Hc,
+                  launch_gcn_layer(s, d, l, B, B, l == 0 ? xt : nullptr, l == 0 ? nullptr : f.h[l - 1], f.h[l], false, true,
+                                   c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, c->ell_c.as<int32_t>(),
+                                   c->ell_v.as<float>(), d.T * d.N, d.N, &w.drop));
+            c->af_stats[5] += 1;
+          }
+        }
+        TRY(run_lstm(c, s, th, ts));
+      } else if (cache) {
+        if (Z == 1) {
+          const int task = a.tasks[r0], wv = a.windows[at];
+          w.F = const_cast<float*>(ptrs[nwin + at]);  // the slot itself
+          if (!c->ad[task].valid[wv]) {
+            TRY(run_gcn(c, s, xt));  // writes the window's features straight into its cache slot
+            c->ad[task].valid[wv] = 1;
+            c->ad_ph.filled += 1;
+          }
+        } else {
+          const float* const* st = nullptr;
+          TRY(xtab_at(c, nwin + at, &st));
+          TIMED(c, s, C_GCN, 0, launch_gather_slabs(s, st, Z, fsz, c->F_main));
+        }
+        TRY(run_lstm(c, s, th, ts));
+      } else {
+        TRY(run_forward(c, s, th, ts, xt));
+      }
+      TIMED(c, s, C_HEAD, 2.0 * Z * w.M * d.HfC * d.H, launch_head_loss(s, d, w, th, ts, c->po, xt, 2.f * inv, true));
+      TRY(run_backward(c, s, th, ts, c->grad));
+      if (train) {
+        // dZ4 = dF through conv4's ReLU, per sample: layer 0's dG slab (left by the BPTT) times W_ih0
+        TIMED(c, s, C_MISC, 2.0 * rows * 4 * d.H * d.Hc,
+              launch_lstm_dx0(s, d, w, w.dG, th + c->po.lay[0].wih, w.F, f.g));
+        const float* x0 = ptrs[at * B];  // B = 1: the window is [T*N][Cin0] in the stream already
+        if (B > 1) {
+          const int64_t xsz = (int64_t)d.T * d.N * d.Cin0;
+          for (int si = 0; si < B; ++si)
+            HIP_TRY(hipMemcpyAsync(f.xcat + si * xsz, ptrs[at * B + si], (size_t)xsz * 4, hipMemcpyDeviceToDevice, s));
+          x0 = f.xcat;
+        }
+        // (conv1's input gradient: nothing reads it)
+        TRY(gcn_backward_chain(c, s, x0, f.h, f.g, f.gn, rows, d.T * d.N, a.gcn, f.ggrad, false,
+                               c->gcn_dz_fused ? f.top : nullptr, c->af_stats, C_MISC));
+        c->af_stats[0] += 1;
+      }
+      // (the step's loss is summed by the Adam launch's first block: the backward leaves the head's partials alone)
+      AdamL2 u{};
+      u.seg[0] = {th, c->grad, a.m + (int64_t)r0 * P, a.v + (int64_t)r0 * P, P};
+      u.seg[1] = {a.gcn, f.ggrad, a.gcn_m, a.gcn_v, Pg};
+      u.S = train ? 2 : 1;
+      u.R = Z;
+      u.part = w.sqpart;
+      u.lr_dev = a.lr_dev + at;
+      for (int z = 0; z < Z; ++z) u.wd.wd[z] = a.wd[r0 + z];
+      u.step = a.step0 + k + 1;
+      u.b1 = a.beta1, u.b2 = a.beta2, u.eps = a.eps, u.max_norm = a.max_norm;
+      u.lpart = w.lpart, u.lblocks = w.lblocks, u.inv_count = inv;
+      u.loss = a.losses + at;
+      u.norm_out = a.norms ? a.norms + at : nullptr;
+      TIMED(c, s, C_MISC, 0, launch_adam_l2(s, u));
     }
-    TIMED(c, s, C_HEAD, 2.0 * c->w.M * d.HfC * d.H, launch_head_loss(s, d, c->w, theta, 0, c->po, xt, 2.f * inv, true));
-    TRY(run_backward(c, s, theta, 0, c->grad));
-    // (the step's loss is summed by the Adam launch's block 0: the backward leaves the head's partials alone)
-    TIMED(c, s, C_MISC, 0,
-          launch_adam_l2(s, theta, c->grad, m, v, P, c->w.sqpart, lr_dev + k, step0 + k + 1, beta1, beta2, eps,
-                         weight_decay, max_norm, c->w.lpart, c->w.lblocks, inv, losses + k));
   }
   if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
   auto t2 = clk::now();
@@ -2407,6 +2581,20 @@ int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float*
   c->w.drop = Drop{};
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
+}
+
+int smaml_adapt_steps(smaml_ctx* c, void* stream, float* theta, float* m, float* v, int32_t step0, int32_t nsteps,
+                      int32_t batch, const int32_t* windows_host, const float* lr_dev, float beta1, float beta2,
+                      float eps, float weight_decay, float max_norm, float* losses) {
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_adapt_steps"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !m || !v || nsteps <= 0 || batch <= 0 || !windows_host || !lr_dev || !losses || step0 < 0)
+    return fail(SMAML_EINVAL, "bad adapt_steps arguments");
+  const int32_t task0 = 0;
+  return adapt_run(c, (hipStream_t)stream,
+                   AdaptCall{&task0, 1, theta, m, v, nullptr, nullptr, nullptr, step0, nsteps, batch, windows_host, lr_dev,
+                             &weight_decay, beta1, beta2, eps, max_norm, losses, nullptr, false});
 }
 
 int smaml_adapt_steps_full(smaml_ctx* c, void* stream, float* theta, float* m, float* v, float* gcn, float* gcn_m,
@@ -2424,115 +2612,10 @@ int smaml_adapt_steps_full(smaml_ctx* c, void* stream, float* theta, float* m, f
   if (!graph_set(c)) return fail(SMAML_ESTATE, "smaml_set_graph not called");
   TRY(check_lstm_dims(c->dims, "smaml_adapt_steps_full"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  const Dims& d = c->d;
-  const int B = batch;
-  const int64_t nptr = (int64_t)nsteps * B;
-  std::vector<const float*> ptrs(nptr);
-  for (int64_t i = 0; i < nptr; ++i) {
-    const int wv = windows_host[i];
-    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[0]) return fail(SMAML_EINVAL, "window start out of range");
-    ptrs[i] = c->feats[0] + (int64_t)wv * d.N * d.Cin0;
-  }
-  if ((int64_t)B * d.T * d.N * std::max(d.Hc, 4 * d.H) >= (1ll << 31))
-    return fail(SMAML_EINVAL, "batch too large: B*T*N*max(Hc, 4H) must stay below 2^31");
-  TRY(ensure_device(c));
-  TRY(check_device_error(c));
-  hipStream_t s = (hipStream_t)stream;
-  // every buffer before the first launch; the feature cache (a frozen base's) is neither allocated nor read
-  const int rps = d.T * d.N, R = B * rps;
-  const int64_t hsz = (int64_t)R * d.Hc, tsz = (int64_t)B * d.N * d.Hc, xsz = B > 1 ? (int64_t)R * d.Cin0 : 0;
-  const int64_t Pg = c->go.total, P = c->po.P;
-  const bool fused_gcn = gcn_mlp_supported(d) && c->kn.gcn_fused;
-  TRY(reserve(c, 1, B));
-  if (c->af_buf.grow((5 * hsz + tsz + xsz + Pg) * 4) != hipSuccess ||
-      c->bw_scratch.grow(2 * (int64_t)R * std::max(d.Hc, d.Cin0) * 4) != hipSuccess ||
-      (fused_gcn && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess) ||
-      c->xtab.grow(std::max<int64_t>(nptr, 1024) * (int64_t)sizeof(float*)) != hipSuccess)
-    return fail(SMAML_ENOMEM, "smaml_adapt_steps_full: hipMalloc of the step's buffers failed (nothing was launched)");
-  float* h[3] = {c->af_buf.as<float>(), c->af_buf.as<float>() + hsz, c->af_buf.as<float>() + 2 * hsz};
-  float* g = h[2] + hsz;
-  float* gn = g + hsz;
-  float* top = gn + hsz;
-  float* xcat = top + tsz;
-  float* ggrad = xcat + xsz;
-  // the gradient's pads are zeroed once per call: every step overwrites the tensors and leaves the pads
-  HIP_TRY(hipMemsetAsync(ggrad, 0, (size_t)Pg * 4, s));
-  // the base trains from here on: gcn is the context's GCN parameter vector, cached features are stale
-  c->gcn = gcn;
-  ad_cache_invalidate(c);
-  for (auto& x : c->af_stats) x = 0;
-  const float inv = 1.f / ((float)d.N * d.HfC * B);
-  const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
-  if (dropout) TRY(upload_task_ids(c, s, 1));
-  set_work(c, 1, B);  // (ends a pending smaml_forward / smaml_backward pair)
-  TRY(upload_xtab(c, s, ptrs.data(), nptr));
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
-  const float* Wih0 = theta + c->po.lay[0].wih;
-  for (int k = 0; k < nsteps; ++k) {
-    Work& w = c->w;
-    const float* const* xt = nullptr;
-    TRY(xtab_at(c, (int64_t)k * B, &xt));
-    if (dropout) set_step_drop(c, step0 + k);
-    if (c->gcn_keep) {
-      TRY(run_gcn_keep(c, s, xt, h, c->af_stats));
-    } else {  // A/B: the frozen-base forward, then conv1..conv3 recomputed on the per-layer path (smaml_backward_base)
-      TRY(run_gcn(c, s, xt));
-      for (int l = 0; l < 3; ++l) {
-        TIMED(c, s, C_GCN, 2.0 * R * c->go.cin[l] * d.Hc,
-              launch_gcn_layer(s, d, l, B, B, l == 0 ? xt : nullptr, l == 0 ? nullptr : h[l - 1], h[l], false, true,
-                               c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, ell_c, ell_v, rps, d.N,
-                               &w.drop));
-        c->af_stats[5] += 1;
-      }
-    }
-    w.consec = 0;
-    TRY(run_lstm(c, s, theta, 0));
-    TIMED(c, s, C_HEAD, 2.0 * w.M * d.HfC * d.H, launch_head_loss(s, d, w, theta, 0, c->po, xt, 2.f * inv, true));
-    TRY(run_backward(c, s, theta, 0, c->grad));
-    // dZ4 = dF through conv4's ReLU, per sample: layer 0's dG slab (left by the BPTT) times W_ih0
-    TIMED(c, s, C_MISC, 2.0 * R * 4 * d.H * d.Hc, launch_lstm_dx0(s, d, w, w.dG, Wih0, w.F, g));
-    const float* x0 = ptrs[(int64_t)k * B];  // B = 1: the window is [T*N][Cin0] in the stream already
-    if (B > 1) {
-      for (int si = 0; si < B; ++si)
-        HIP_TRY(hipMemcpyAsync(xcat + (int64_t)si * rps * d.Cin0, ptrs[(int64_t)k * B + si], (size_t)rps * d.Cin0 * 4,
-                               hipMemcpyDeviceToDevice, s));
-      x0 = xcat;
-    }
-    const float sc = w.drop.gcn() ? w.drop.sc_gcn : 1.f;
-    for (int l = 3; l >= 0; --l) {
-      // dW, db of conv l+1 from its pre-activation gradient g and its input
-      TRY(gcn_conv_bwd(c, s, l == 0 ? x0 : h[l - 1], R, rps, c->go.cin[l], gcn + c->go.w[l], d.Hc, g, d.N, nullptr, ggrad,
-                       c->go.w[l], c->go.b[l]));
-      if (l == 0) break;  // (conv1's input gradient: nothing reads it)
-      // through A_hat^T, then the dropout (its mask replayed) and the ReLU after conv l
-      const float* W = gcn + c->go.w[l];
-      if (c->gcn_dz_fused) {
-        TIMED(c, s, C_MISC, 2.0 * R * d.Hc * d.Hc,
-              launch_gcn_dz(s, g, R, d.Hc, W, d.Hc, h[l - 1], sc, rps, d.N, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
-                            c->tr_v.as<float>(), top, gn));
-        c->af_stats[3] += 1;
-      } else {
-        float* t1 = c->bw_scratch.as<float>() + (int64_t)R * std::max(d.Hc, d.Cin0);
-        TIMED(c, s, C_MISC, 2.0 * R * d.Hc * d.Hc, {
-          launch_gemm_nn_plain(s, g, R, d.Hc, W, d.Hc, t1);
-          launch_gather_rows(s, t1, gn, R, d.Hc, d.N, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
-                             c->tr_v.as<float>(), rps);
-          launch_drop_relu_grad(s, gn, h[l - 1], hsz, sc);
-        });
-        c->af_stats[4] += 3;
-      }
-      std::swap(g, gn);
-    }
-    TIMED(c, s, C_MISC, 0,
-          launch_adam_l2_joint(s, theta, c->grad, m, v, P, gcn, ggrad, gcn_m, gcn_v, Pg, c->w.sqpart, lr_dev + k,
-                               step0 + k + 1, beta1, beta2, eps, weight_decay, max_norm, c->w.lpart, c->w.lblocks, inv,
-                               losses + k, norms ? norms + k : nullptr));
-    c->af_stats[0] += 1;
-  }
-  c->w.drop = Drop{};
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
+  const int32_t task0 = 0;
+  return adapt_run(c, (hipStream_t)stream,
+                   AdaptCall{&task0, 1, theta, m, v, gcn, gcn_m, gcn_v, step0, nsteps, batch, windows_host, lr_dev,
+                             &weight_decay, beta1, beta2, eps, max_norm, losses, norms, false});
 }
 
 int smaml_adapt_full_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
@@ -2554,17 +2637,13 @@ int smaml_adapt_prepare_multi(smaml_ctx* c, void* stream, int32_t nregions, cons
   return ad_prepare(c, (hipStream_t)stream, batch, tasks_host, nregions, &cache);
 }
 
-// R regions' fine-tuning in lockstep: step k of every region of a group as ONE set of launches over the
-// task axis (Z = the group's regions, per-task parameters at stride P), as the MAML inner loop runs its
-// tasks. The regions of a group are consecutive entries of tasks_host, so their theta / m / v / lr /
-// loss slabs are the caller's arrays at the group's offset. With the feature cache, the step's R slots
-// (one per region, anywhere in that region's cache) are gathered into the workspace's contiguous F by one
-// copy launch from a device table of slot pointers uploaded with the window table (k_gather_slabs).
+// R regions' fine-tuning in lockstep (adapt_run): step k of every region of a launch set as ONE set of launches
+// over the task axis, as the MAML inner loop runs its tasks. The regions of a set are consecutive entries of
+// tasks_host, so their theta / m / v / lr / loss slabs are the caller's arrays at the set's offset.
 int smaml_adapt_steps_multi(smaml_ctx* c, void* stream, int32_t nregions, const int32_t* tasks_host, float* theta,
                             float* m, float* v, int32_t step0, int32_t nsteps, int32_t batch,
                             const int32_t* windows_host, const float* lr_dev, const float* weight_decay_host,
                             float beta1, float beta2, float eps, float max_norm, float* losses) {
-  using clk = std::chrono::steady_clock;
   TRY(require_ready(c));
   TRY(check_lstm_dims(c->dims, "smaml_adapt_steps_multi"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
@@ -2572,88 +2651,9 @@ int smaml_adapt_steps_multi(smaml_ctx* c, void* stream, int32_t nregions, const 
       step0 < 0)
     return fail(SMAML_EINVAL, "bad adapt_steps_multi arguments");
   TRY(ad_check_tasks(c, "adapt_steps_multi", nregions, tasks_host));
-  TRY(ensure_device(c));
-  hipStream_t s = (hipStream_t)stream;
-  const Dims& d = c->d;
-  const int B = batch, R = nregions;
-  const int64_t fsz = (int64_t)d.T * d.N * d.Hc;  // floats of one window's features
-  // one table for the call: the window pointers [nsteps][R][B], then the cache-slot pointers [nsteps][R]
-  const int64_t nwin = (int64_t)nsteps * R * B, nslot = (int64_t)nsteps * R;
-  std::vector<const float*> ptrs(nwin + nslot, nullptr);
-  for (int64_t i = 0; i < nwin; ++i) {
-    const int r = (int)(i / B % R), task = tasks_host[r];
-    const int wv = windows_host[i];
-    if (wv < 0 || wv + d.T + d.Hf >= c->t_total[task])
-      return fail(SMAML_EINVAL, "adapt_steps_multi: region " + std::to_string(r) + " (task " + std::to_string(task) +
-                                    "): window " + std::to_string(wv) + " of step " + std::to_string(i / B / R) +
-                                    " out of range (stream of " + std::to_string(c->t_total[task]) + " rows)");
-    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
-  }
-  c->ad_ph = AdPhases{};
-  bool cache = false;
-  TRY(ad_prepare(c, s, B, tasks_host, R, &cache));  // no allocation after smaml_adapt_prepare_multi / an earlier call
-  const int G = ad_group_size(c, R);  // regions per launch set
-  const int64_t P = c->po.P;
-  const float inv = 1.f / ((float)d.N * d.HfC * B);
-  const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
-  if (dropout) {  // masks keyed by each region's task id (smaml_set_task_ids; default: the task index)
-    std::vector<int32_t> ids(R);
-    for (int r = 0; r < R; ++r) ids[r] = tasks_host[r] < (int)c->task_ids.size() ? c->task_ids[tasks_host[r]] : tasks_host[r];
-    TRY(c->stage.upload(s, c->task_id_dev, ids.data(), (int64_t)R * 4));
-  }
-  auto t0 = clk::now();
-  if (cache) {
-    // every region's missing windows up front, region by region (cache is on only at B = 1: [nsteps][R])
-    for (int r = 0; r < R; ++r) TRY(ad_cache_fill(c, s, tasks_host[r], windows_host + r, nsteps, R));
-    if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < nslot; ++i)
-      ptrs[nwin + i] = c->ad[tasks_host[i % R]].F.as<float>() + (int64_t)windows_host[i] * fsz;
-  }
-  auto t1 = clk::now();
-  TRY(upload_xtab(c, s, ptrs.data(), nwin + nslot));
-  for (int k = 0; k < nsteps; ++k) {
-    for (int r0 = 0; r0 < R; r0 += G) {
-      const int Z = std::min(G, R - r0);
-      set_work(c, Z, B);
-      // (one region: the parameters at stride 0, as smaml_adapt_steps passes them)
-      float* th = theta + (int64_t)r0 * P;
-      const int64_t ts = Z > 1 ? P : 0;
-      const float* const* xt = nullptr;
-      TRY(xtab_at(c, ((int64_t)k * R + r0) * B, &xt));
-      if (dropout) {
-        set_step_drop(c, step0 + k);
-        c->w.drop.task_id = c->task_id_dev + r0;
-      }
-      if (cache) {
-        if (Z == 1) {
-          c->w.F = const_cast<float*>(ptrs[nwin + (int64_t)k * R + r0]);  // the slot itself
-        } else {
-          const float* const* st = nullptr;
-          TRY(xtab_at(c, nwin + (int64_t)k * R + r0, &st));
-          TIMED(c, s, C_GCN, 0, launch_gather_slabs(s, st, Z, fsz, c->F_main));
-        }
-        TRY(run_lstm(c, s, th, ts));
-      } else {
-        TRY(run_forward(c, s, th, ts, xt));
-      }
-      TIMED(c, s, C_HEAD, 2.0 * Z * c->w.M * d.HfC * d.H, launch_head_loss(s, d, c->w, th, ts, c->po, xt, 2.f * inv, true));
-      TRY(run_backward(c, s, th, ts, c->grad));
-      AdamWd wds{};
-      for (int z = 0; z < Z; ++z) wds.wd[z] = weight_decay_host[r0 + z];
-      TIMED(c, s, C_MISC, 0,
-            launch_adam_l2_multi(s, th, c->grad, m + (int64_t)r0 * P, v + (int64_t)r0 * P, P, Z, c->w.sqpart,
-                                 lr_dev + (int64_t)k * R + r0, step0 + k + 1, beta1, beta2, eps, wds, max_norm,
-                                 c->w.lpart, c->w.lblocks, inv, losses + (int64_t)k * R + r0));
-    }
-  }
-  if (c->ad_phase_sync) HIP_TRY(hipStreamSynchronize(s));
-  auto t2 = clk::now();
-  c->ad_ph.ms[AD_FILL] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  c->ad_ph.ms[AD_STEPS] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-  c->w.F = c->F_main;
-  c->w.drop = Drop{};
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
+  return adapt_run(c, (hipStream_t)stream,
+                   AdaptCall{tasks_host, nregions, theta, m, v, nullptr, nullptr, nullptr, step0, nsteps, batch,
+                             windows_host, lr_dev, weight_decay_host, beta1, beta2, eps, max_norm, losses, nullptr, true});
 }
 
 int smaml_adapt_phases(const smaml_ctx* c, double* ms, int32_t cap, int32_t* count, int64_t* filled) {
@@ -2884,14 +2884,9 @@ int smaml_backward_base(smaml_ctx* c, void* stream, const float* theta, const fl
       HIP_TRY(hipMemcpyAsync(xcat + (int64_t)si * rps * d.Cin0, x_host[si], (size_t)rps * d.Cin0 * 4,
                              hipMemcpyDeviceToDevice, s));
   }
-  for (int k = 3; k >= 0; --k) {
-    // through the dropout (its mask replayed) and the ReLU after conv k+1; conv4's ReLU is in dZ4 already
-    if (k < 3) launch_drop_relu_grad(s, g, h[k], hsz, w.drop.gcn() ? w.drop.sc_gcn : 1.f);
-    float* dx = k > 0 || dx_host ? gn : nullptr;
-    TRY(gcn_conv_bwd(c, s, k == 0 ? xcat : h[k - 1], R, rps, c->go.cin[k], c->gcn + c->go.w[k], d.Hc, g, d.N, dx, gcn_grad,
-                     c->go.w[k], c->go.b[k]));
-    std::swap(g, gn);
-  }
+  // conv4 -> conv1 (conv4's ReLU is in dZ4 already), the three-launch form of the layer-to-layer gradient; timed
+  // with the recompute above (C_GCN), so that C_MISC stays the layer-0 input gradient alone (tools/bench_base_grad.py)
+  TRY(gcn_backward_chain(c, s, xcat, h, g, gn, R, rps, c->gcn, gcn_grad, dx_host != nullptr, nullptr, nullptr, C_GCN));
   if (dx_host)
     for (int si = 0; si < nsamples; ++si)
       HIP_TRY(hipMemcpyAsync(dx_host[si], g + (int64_t)si * rps * d.Cin0, (size_t)rps * d.Cin0 * 4,

@@ -633,32 +633,38 @@ void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, i
                   float lr, float b1, float b2, float eps, float wd, float step_size, float bc2_sqrt,
                   float max_norm, float* norm_out);
 
-// loss != null: block 0 also writes the step's loss from the head's partials (launch_loss_final's sum)
-void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double* part,
-                    const float* lr_dev, int step, float b1, float b2, float eps, float wd, float max_norm,
-                    const float* lpart, int lblocks, float inv_count, float* loss);
-
-// launch_adam_l2 over TWO vectors clipped by their joint norm (smaml_adapt_steps_full: the trainable vector
-// p1 [n1] and the GCN vector p2 [n2]): k_sqsum2 writes part [2][SQB] (p1's partials, then p2's), then
-// k_adam_l2_joint takes the clip coefficient from all 2 SQB partials in that order, updates both segments
-// with k_adam_l2's element arithmetic, sums the loss in block 0 and writes the joint norm (before clipping)
-// to norm_out (may be null).
-void launch_adam_l2_joint(hipStream_t s, float* p1, const float* g1, float* m1, float* v1, int64_t n1, float* p2,
-                          const float* g2, float* m2, float* v2, int64_t n2, double* part, const float* lr_dev,
-                          int step, float b1, float b2, float eps, float wd, float max_norm, const float* lpart,
-                          int lblocks, float inv_count, float* loss, float* norm_out);
-
-// launch_adam_l2 for R regions in lockstep (smaml_adapt_steps_multi), region r on blockIdx.y: p, g, m, v
-// [R][n], part [R][SQB], lr_dev [R], lpart [R][lblocks], loss [R]; each region clips by its own norm,
-// steps at its own learning rate and weight decay and sums its own loss. Element arithmetic and the
-// host-computed bias corrections are launch_adam_l2's.
-constexpr int ADAPT_MAX_GROUP = 64;  // regions per launch set (the weight decays travel as a kernel argument)
+// The adaptation step's clip_grad_norm_ + Adam(L2) for R regions x S segments (S = 1: the trainable vector;
+// S = 2: the trainable vector and the GCN vector clipped by their joint norm), two launches (k_sqsum,
+// k_adam_l2; the invariants that keep every result bit are stated above k_adam_l2). Per segment p, g, m, v
+// are [R][n] (region stride n); part [R][S][SQB]; lr_dev [R]; wd.wd[r] region r's weight decay; lpart
+// [R][lblocks] the head's loss partials; loss [R] (null: not summed) and norm_out [R] (null: not written) the
+// step's loss and its gradient norm before clipping. R <= ADAPT_MAX_GROUP (grid z, and the weight decays travel
+// as a kernel argument).
+constexpr int ADAPT_MAX_GROUP = 64;  // regions per launch set
 struct AdamWd {
   float wd[ADAPT_MAX_GROUP];
 };
-void launch_adam_l2_multi(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, int R, double* part,
-                          const float* lr_dev, int step, float b1, float b2, float eps, const AdamWd& wd,
-                          float max_norm, const float* lpart, int lblocks, float inv_count, float* loss);
+struct AdamSeg {
+  float* p;
+  const float* g;
+  float *m, *v;
+  int64_t n;
+};
+struct AdamL2 {
+  AdamSeg seg[2];
+  int S, R;
+  double* part;
+  const float* lr_dev;
+  AdamWd wd;
+  int step;  // Adam's step count of this update (>= 1)
+  float b1, b2, eps, max_norm;
+  const float* lpart;
+  int lblocks;
+  float inv_count;
+  float* loss;
+  float* norm_out;
+};
+void launch_adam_l2(hipStream_t s, const AdamL2& a);
 // dst [Z][n] <- tab[z][0 .. n) (device table of Z source pointers): the lockstep step's features, one
 // cache slot per region, into the workspace's contiguous F
 void launch_gather_slabs(hipStream_t s, const float* const* tab, int Z, int64_t n, float* dst);

@@ -2963,10 +2963,18 @@ void launch_gemm_nt(hipStream_t s, const float* A, int64_t a_zstride, int rows, 
 
 // ====================================================================================
 // clip_grad_norm_ + SGD, per task z. Squared norm accumulated in fp64, fixed order.
-__global__ void k_sqsum(const float* __restrict__ g, int64_t P, double* __restrict__ part) {
+// Grid (SQB, S, R): segment s = blockIdx.y of S = gridDim.y gradient vectors (1 or 2: sg.g[s], sg.n[s] elements
+// per region), region / task r = blockIdx.z at stride n_s. Partials laid out part[r][s][SQB], each over
+// per = ceil(n_s / SQB) elements.
+struct SqSegs {
+  const float* g[2];
+  int64_t n[2];
+};
+__global__ void k_sqsum(SqSegs sg, double* __restrict__ part) {
   __shared__ double red[NT / 64];
-  const int z = blockIdx.y;
-  const float* gz = g + (int64_t)z * P;
+  const int sn = blockIdx.y, z = blockIdx.z;
+  const int64_t P = sn ? sg.n[1] : sg.n[0];
+  const float* gz = (sn ? sg.g[1] : sg.g[0]) + (int64_t)z * P;
   const int64_t per = (P + SQB - 1) / SQB;
   const int64_t b = (int64_t)blockIdx.x * per, e = b + per < P ? b + per : P;
   double acc = 0.0;
@@ -2977,20 +2985,21 @@ __global__ void k_sqsum(const float* __restrict__ g, int64_t P, double* __restri
     acc += v * v;
   }
   const double s = block_sum_d(acc, red);
-  if (threadIdx.x == 0) part[(int64_t)z * SQB + blockIdx.x] = s;
+  if (threadIdx.x == 0) part[((int64_t)z * gridDim.y + sn) * SQB + blockIdx.x] = s;
 }
 
-
+// (COUNT partials in index order: SQB of one vector, S * SQB of S vectors clipped jointly. A compile-time count:
+// the loads go out together; with a run-time count they went one by one and the batch-1 step measured 4 us
+// slower at 64 partials, 13 us at 128, profiles/adapt_step_refactor.log)
+template <int COUNT = SQB>
 __device__ __forceinline__ float clip_coef_from(const double* part, float max_norm, float* total_out) {
   double t = 0.0;
-  for (int i = 0; i < SQB; ++i) t += part[i];
+  for (int i = 0; i < COUNT; ++i) t += part[i];
   const float total = (float)sqrt(t);
   if (total_out) *total_out = total;
   const float coef = max_norm / (total + 1e-6f);
   return coef < 1.f ? coef : 1.f;
 }
-
-
 
 // The inner SGD step as ONE kernel (train_hybrid_maml_v5.py:135-139: clip_grad_norm_ + SGD): every
 // block computes the fp64 squared-norm partials of its (task, chunk) items -- the partition and order
@@ -3121,7 +3130,7 @@ __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, floa
 void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double* part,
                   float lr, float b1, float b2, float eps, float wd, float step_size, float bc2_sqrt,
                   float max_norm, float* norm_out) {
-  k_sqsum<<<dim3(SQB, 1), NT, 0, s>>>(g, n, part);
+  k_sqsum<<<dim3(SQB, 1, 1), NT, 0, s>>>(SqSegs{{g, nullptr}, {n, 0}}, part);
   int nb = (int)((n + NT - 1) / NT);
   if (nb > 2048) nb = 2048;
   k_adamw<<<nb, NT, 0, s>>>(p, g, m, v, n, part, lr, b1, b2, eps, wd, step_size, bc2_sqrt, max_norm, norm_out);
@@ -3129,23 +3138,47 @@ void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, i
 
 // ====================================================================================
 // Regional adaptation step (adapt_hybrid_v5.py:196-201): clip_grad_norm_(max_norm) then
-// torch.optim.Adam with coupled L2 weight decay (g += wd * p), per-step learning rate.
-// bc1 = 1 - b1^step and bc2_sqrt = sqrt(1 - b2^step) come from the host (the step is a host integer):
-// a per-thread fp64 pow was most of this kernel's time at batch 1.
-__global__ void k_adam_l2(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                          float* __restrict__ v, int64_t n, const double* __restrict__ part, const float* __restrict__ lr_dev,
-                          double bc1, float bc2_sqrt, float b1, float b2, float eps, float wd, float max_norm,
-                          const float* __restrict__ lpart, int lblocks, float inv_count, float* __restrict__ loss) {
-  if (loss && blockIdx.x == 0) {  // the step's loss from the head's partials: k_loss_final's sum, same order
+// torch.optim.Adam with coupled L2 weight decay (g += wd * p), per-step learning rate, for R regions x S
+// segments in one launch pair (launch_adam_l2): grid (blocks, S, R), segment s = blockIdx.y, region r =
+// blockIdx.z, every per-segment vector [R][n_s]. What keeps every result bit, whatever R and S:
+//  - partials: k_sqsum's, part[r][s][SQB], each over per = ceil(n_s / SQB) elements (per-thread stride NT,
+//    `#pragma unroll 8`, block_sum_d);
+//  - clip coefficient of region r: the fp64 sum of its S * SQB partials in index order, (float)sqrt,
+//    max_norm / (total + 1e-6f) clamped at 1 (clip_coef_from): one vector's norm at S = 1, the joint norm
+//    of both at S = 2, written before clipping to norm_out[r] when set;
+//  - loss: block x = 0 of segment 0 of region r sums the head's partials lpart + r * lblocks in
+//    k_loss_final's order into loss[r];
+//  - bc1 = 1 - b1^step and bc2_sqrt = sqrt(1 - b2^step) come from the host in fp64 (the step is a host
+//    integer: a per-thread fp64 pow was most of this kernel's time at batch 1);
+//  - the element update is the four lines below, over a grid-stride loop: the result does not depend on the
+//    grid size (min(2048, ceil(max_s n_s / NT)) blocks per (r, s)).
+// S is a template parameter for the coefficient's compile-time count; the weight decays come last so that one
+// region's arguments stay within the first 256 bytes of the argument block.
+template <int S>
+__global__ void k_adam_l2(AdamSeg s0, AdamSeg s1, const double* __restrict__ part, const float* __restrict__ lr_dev,
+                          double bc1, float bc2_sqrt, float b1, float b2, float eps, float max_norm,
+                          const float* __restrict__ lpart, int lblocks, float inv_count, float* __restrict__ loss,
+                          float* __restrict__ norm_out, AdamWd wds) {
+  const int sn = blockIdx.y, r = blockIdx.z;  // (S = gridDim.y)
+  const bool first = blockIdx.x == 0 && sn == 0;
+  if (loss && first) {  // the step's loss from the head's partials: k_loss_final's sum, same order
     __shared__ float red[NT / 64];
+    const float* lp = lpart + (int64_t)r * lblocks;
     float a = 0.f;
-    for (int i = threadIdx.x; i < lblocks; i += NT) a += lpart[i];
+    for (int i = threadIdx.x; i < lblocks; i += NT) a += lp[i];
     const float s = block_sum(a, red);
-    if (threadIdx.x == 0) *loss = s * inv_count;
+    if (threadIdx.x == 0) loss[r] = s * inv_count;
   }
   float total;
-  const float coef = clip_coef_from(part, max_norm, &total);
-  const float lr = *lr_dev;
+  const float coef = clip_coef_from<S * SQB>(part + (int64_t)r * S * SQB, max_norm, &total);
+  if (norm_out && first && threadIdx.x == 0) norm_out[r] = total;
+  const int64_t n = sn ? s1.n : s0.n;
+  float* __restrict__ p = (sn ? s1.p : s0.p) + (int64_t)r * n;
+  const float* __restrict__ g = (sn ? s1.g : s0.g) + (int64_t)r * n;
+  float* __restrict__ m = (sn ? s1.m : s0.m) + (int64_t)r * n;
+  float* __restrict__ v = (sn ? s1.v : s0.v) + (int64_t)r * n;
+  const float lr = lr_dev[r];
+  const float wd = wds.wd[r];
   const float step_size = (float)((double)lr / bc1);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float gi = fmaf(wd, p[i], g[i] * coef);
@@ -3160,142 +3193,16 @@ __global__ void k_adam_l2(float* __restrict__ p, const float* __restrict__ g, fl
 // (measured: the same update as ONE grid-barrier launch -- k_sqsum's partials, a grid barrier over ~512
 // blocks, the element update -- took 81 us per sample-step against 23 for these two launches,
 // profiles/r04_rocprof_adapt_kw.md: 512 arrivals on one counter cost more than a launch boundary)
-void launch_adam_l2(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double* part,
-                    const float* lr_dev, int step, float b1, float b2, float eps, float wd, float max_norm,
-                    const float* lpart, int lblocks, float inv_count, float* loss) {
-  int nb = (int)((n + NT - 1) / NT);
-  if (nb > 2048) nb = 2048;
-  k_sqsum<<<dim3(SQB, 1), NT, 0, s>>>(g, n, part);
-  const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
-  k_adam_l2<<<nb, NT, 0, s>>>(p, g, m, v, n, part, lr_dev, bc1, (float)std::sqrt(bc2), b1, b2, eps, wd, max_norm,
-                              lpart, lblocks, inv_count, loss);
-}
-
-// Whole-model adaptation step (smaml_adapt_steps_full): clip_grad_norm_ over the gradients of TWO vectors
-// jointly, then Adam on both. k_sqsum2: k_sqsum's partials of vector 1 (blockIdx.y = 0) into part[0 .. SQB)
-// and of vector 2 (blockIdx.y = 1) into part[SQB .. 2 SQB) in one launch.
-__global__ void k_sqsum2(const float* __restrict__ g1, int64_t n1, const float* __restrict__ g2, int64_t n2,
-                         double* __restrict__ part) {
-  __shared__ double red[NT / 64];
-  const int z = blockIdx.y;
-  const float* gz = z == 0 ? g1 : g2;
-  const int64_t P = z == 0 ? n1 : n2;
-  const int64_t per = (P + SQB - 1) / SQB;
-  const int64_t b = (int64_t)blockIdx.x * per, e = b + per < P ? b + per : P;
-  double acc = 0.0;
-#pragma unroll 8
-  for (int64_t i = b + threadIdx.x; i < e; i += NT) {
-    const double v = gz[i];
-    acc += v * v;
-  }
-  const double s = block_sum_d(acc, red);
-  if (threadIdx.x == 0) part[(int64_t)z * SQB + blockIdx.x] = s;
-}
-
-// k_adam_l2 on both vectors (segment = blockIdx.y) with the clip coefficient of the joint norm: the sum of
-// all 2 SQB partials in order (vector 1's, then vector 2's). Block (0, 0) sums the loss as k_adam_l2 does and
-// writes the joint norm before clipping. The element arithmetic is k_adam_l2's, expression for expression.
-__global__ void k_adam_l2_joint(float* __restrict__ p1, const float* __restrict__ g1, float* __restrict__ m1,
-                                float* __restrict__ v1, int64_t n1, float* __restrict__ p2,
-                                const float* __restrict__ g2, float* __restrict__ m2, float* __restrict__ v2,
-                                int64_t n2, const double* __restrict__ part, const float* __restrict__ lr_dev,
-                                double bc1, float bc2_sqrt, float b1, float b2, float eps, float wd, float max_norm,
-                                const float* __restrict__ lpart, int lblocks, float inv_count,
-                                float* __restrict__ loss, float* __restrict__ norm_out) {
-  const bool first = blockIdx.x == 0 && blockIdx.y == 0;
-  if (loss && first) {
-    __shared__ float red[NT / 64];
-    float a = 0.f;
-    for (int i = threadIdx.x; i < lblocks; i += NT) a += lpart[i];
-    const float s = block_sum(a, red);
-    if (threadIdx.x == 0) *loss = s * inv_count;
-  }
-  double t = 0.0;
-  for (int i = 0; i < 2 * SQB; ++i) t += part[i];
-  const float total = (float)sqrt(t);
-  if (norm_out && first && threadIdx.x == 0) *norm_out = total;
-  float coef = max_norm / (total + 1e-6f);
-  coef = coef < 1.f ? coef : 1.f;
-  const bool seg2 = blockIdx.y != 0;
-  float* __restrict__ p = seg2 ? p2 : p1;
-  const float* __restrict__ g = seg2 ? g2 : g1;
-  float* __restrict__ m = seg2 ? m2 : m1;
-  float* __restrict__ v = seg2 ? v2 : v1;
-  const int64_t n = seg2 ? n2 : n1;
-  const float lr = *lr_dev;
-  const float step_size = (float)((double)lr / bc1);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = fmaf(wd, p[i], g[i] * coef);
-    const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    p[i] = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
-// (two launches, as launch_adam_l2: see the measurement above it)
-void launch_adam_l2_joint(hipStream_t s, float* p1, const float* g1, float* m1, float* v1, int64_t n1, float* p2,
-                          const float* g2, float* m2, float* v2, int64_t n2, double* part, const float* lr_dev,
-                          int step, float b1, float b2, float eps, float wd, float max_norm, const float* lpart,
-                          int lblocks, float inv_count, float* loss, float* norm_out) {
-  const int64_t nmax = n1 > n2 ? n1 : n2;
+void launch_adam_l2(hipStream_t s, const AdamL2& a) {
+  const AdamSeg s0 = a.seg[0], s1 = a.S > 1 ? a.seg[1] : AdamSeg{};
+  const int64_t nmax = s0.n > s1.n ? s0.n : s1.n;
   int nb = (int)((nmax + NT - 1) / NT);
   if (nb > 2048) nb = 2048;
-  k_sqsum2<<<dim3(SQB, 2), NT, 0, s>>>(g1, n1, g2, n2, part);
-  const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
-  k_adam_l2_joint<<<dim3(nb, 2), NT, 0, s>>>(p1, g1, m1, v1, n1, p2, g2, m2, v2, n2, part, lr_dev, bc1,
-                                             (float)std::sqrt(bc2), b1, b2, eps, wd, max_norm, lpart, lblocks,
-                                             inv_count, loss, norm_out);
-}
-
-// k_adam_l2 for R regions adapted in lockstep, region r = blockIdx.y: its own parameter / moment / gradient
-// slabs, clip coefficient (its SQB partials), learning rate, weight decay and loss (its head partials,
-// summed in k_adam_l2's order). The element arithmetic is k_adam_l2's, expression for expression, so a
-// region computes bitwise what the single-region kernel computes from the same inputs.
-__global__ void k_adam_l2_multi(float* __restrict__ p_all, const float* __restrict__ g_all, float* __restrict__ m_all,
-                                float* __restrict__ v_all, int64_t n, const double* __restrict__ part_all,
-                                const float* __restrict__ lr_dev, double bc1, float bc2_sqrt, float b1, float b2,
-                                float eps, AdamWd wds, float max_norm, const float* __restrict__ lpart_all,
-                                int lblocks, float inv_count, float* __restrict__ loss) {
-  const int r = blockIdx.y;
-  float* __restrict__ p = p_all + (int64_t)r * n;
-  const float* __restrict__ g = g_all + (int64_t)r * n;
-  float* __restrict__ m = m_all + (int64_t)r * n;
-  float* __restrict__ v = v_all + (int64_t)r * n;
-  if (loss && blockIdx.x == 0) {
-    __shared__ float red[NT / 64];
-    const float* lpart = lpart_all + (int64_t)r * lblocks;
-    float a = 0.f;
-    for (int i = threadIdx.x; i < lblocks; i += NT) a += lpart[i];
-    const float s = block_sum(a, red);
-    if (threadIdx.x == 0) loss[r] = s * inv_count;
-  }
-  float total;
-  const float coef = clip_coef_from(part_all + (int64_t)r * SQB, max_norm, &total);
-  const float lr = lr_dev[r];
-  const float wd = wds.wd[r];
-  const float step_size = (float)((double)lr / bc1);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = fmaf(wd, p[i], g[i] * coef);
-    const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    p[i] = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
-// (two launches, as launch_adam_l2: see the measurement above it)
-void launch_adam_l2_multi(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, int R, double* part,
-                          const float* lr_dev, int step, float b1, float b2, float eps, const AdamWd& wd,
-                          float max_norm, const float* lpart, int lblocks, float inv_count, float* loss) {
-  int nb = (int)((n + NT - 1) / NT);
-  if (nb > 2048) nb = 2048;
-  k_sqsum<<<dim3(SQB, R), NT, 0, s>>>(g, n, part);
-  const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
-  k_adam_l2_multi<<<dim3(nb, R), NT, 0, s>>>(p, g, m, v, n, part, lr_dev, bc1, (float)std::sqrt(bc2), b1, b2, eps, wd,
-                                             max_norm, lpart, lblocks, inv_count, loss);
+  k_sqsum<<<dim3(SQB, a.S, a.R), NT, 0, s>>>(SqSegs{{s0.g, s1.g}, {s0.n, s1.n}}, a.part);
+  const double bc1 = 1.0 - std::pow((double)a.b1, a.step), bc2 = 1.0 - std::pow((double)a.b2, a.step);
+  (a.S > 1 ? k_adam_l2<2> : k_adam_l2<1>)<<<dim3(nb, a.S, a.R), NT, 0, s>>>(
+      s0, s1, a.part, a.lr_dev, bc1, (float)std::sqrt(bc2), a.b1, a.b2, a.eps, a.max_norm, a.lpart, a.lblocks,
+      a.inv_count, a.loss, a.norm_out, a.wd);
 }
 
 // dst [Z][n] <- tab[z][0 .. n): 16-byte copies when n and every pointer allow it (vec), else by element.
