@@ -46,7 +46,7 @@ typedef struct smaml_ctx smaml_ctx;
  * lstm_num_layers <= 8, forecast_horizon * output_channels <= 128, output_channels <= input_channels.
  * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_backward_base, smaml_lstm_forward,
  * smaml_lstm_backward, smaml_head_loss, smaml_meta_step, smaml_inner_loop, smaml_adapt_prepare[_multi],
- * smaml_adapt_steps[_multi, _full], smaml_forecast, smaml_forecast_ensemble) requires in addition
+ * smaml_adapt_steps[_multi, _full], smaml_forecast, smaml_forecast_ensemble, smaml_forecast_rollout) requires in addition
  *   hidden_channels % 16 == 0                        (the layer-0 K segment of the gate-GEMM tile loaders)
  *   (forecast_horizon * output_channels) % 4 == 0    (16-byte reads of prediction rows)
  * and returns SMAML_EINVAL naming the dimension otherwise, before it allocates or launches anything. */
@@ -187,6 +187,52 @@ int smaml_forecast(smaml_ctx* ctx, void* stream, const float* theta, int32_t tas
 /* Bytes of device memory the forecast's own buffers hold (not part of smaml_workspace_bytes; those of
  * smaml_forecast_ensemble included). */
 int64_t smaml_forecast_bytes(const smaml_ctx* ctx);
+
+/* Autoregressive rollout: the forecast fed back in, to reach lead times past the model's Hf steps. New; the
+ * reference forecasts one horizon per window only. Stride s = Hf + 1.
+ *   Origin o (a window start in task `task`'s stream S) gets a private sequence X, rows [N][Cin]:
+ *   X[rho] = S[o + rho] for rho < T. Cycle j = 0 .. R-1 (R = `cycles`): the window is X[j s : j s + T]; the
+ *   eval-mode output is P flat [N*Hf][C], read as [Hf][N][C] -- the F4 pairing the model was trained with
+ *   (flat row r is lead h' = r / N, node n' = r % N). With rho0 = j s + T the cycle appends
+ *     X[rho0 + 1 + h'][n'][c] = P[h'][n'][c]                                  for c < C,
+ *     X[rho0][n][c] = 0.5f * (X[rho0 - 1][n][c] + P[0][n][c]) in f32          gap = 1 (midpoint), or
+ *     X[rho0][n][c] = X[rho0 - 1][n][c]                                       gap = 0 (persistence):
+ *   the targets skip t + 0 (F5), so row rho0 is a gap no forecast covers. Channels c >= C of every appended
+ *   row are S[o + rho][n][c]: the caller registers a stream whose rows past the last observation carry valid
+ *   exogenous (calendar, Koppen) channels; the weather channels of those rows are never read as inputs and
+ *   may be NaN.
+ *   Checked before anything is allocated or launched (SMAML_EINVAL naming the origin): o >= 0,
+ *   o + T + (R - 1) s <= t_total, with `skill` o + T + R s <= t_total. traj and skill both NULL, cycles <= 0,
+ *   gap outside {0, 1}, norig or batch <= 0: SMAML_EINVAL before a context or device is needed.
+ *   traj (device, optional) [norig][R][s][N][C], normalised: the weather channels of the appended rows; row 0
+ *   of each cycle is the gap row, rows 1..Hf the memory image of P, bit for bit.
+ *   skill (device doubles, optional) [3][R s][C], overwritten: per absolute lead k = j s + i and variable,
+ *   sums over origins and nodes of every traj row x against y = S[o + T + k]:
+ *     [0] sum (s_c (x - y))^2, [1] sum |s_c (x - y)|, [2] sum (s_c (y_last - y))^2, y_last = S[o + T - 1],
+ *   s_c = scale_host[c] (NULL = 1). Fixed order as smaml_forecast's sums (f32 per block, double across blocks
+ *   and passes): bitwise repeatable.
+ * The origins run in passes of at most `batch`; all origins of a pass advance in lockstep through the R cycles.
+ * The private sequences live on the device and k_rollout_append writes each cycle's rows into them (one launch
+ * per cycle over the pass), so nothing is copied or uploaded between cycles: one pointer table per call. Layer
+ * 0's input projection is kept across cycles in a slot table [S][M][4H] (M = B N; private row rho in slot
+ * rho % S, S = T) that k_lstm_fwd_infer reads through XgDedup's second addressing mode; per cycle only the rows
+ * the previous cycle appended go through the position-independent GCN (the row-run form of k_gcn_mlp, or the
+ * per-layer kernels) and the projection, while the window's t = 0 rows, whose features aggregate over the graph
+ * (F3), are recomputed every cycle into a block of their own. smaml_set_option("roll_reuse", 0) recomputes
+ * every row of every window each cycle through the same kernels into the same table: bitwise the same results.
+ * State isolation as smaml_forecast: buffers of its own (grow only, in smaml_forecast_bytes), the workspace, the
+ * adaptation cache and the meta-step state untouched, a pending smaml_forward / smaml_backward pair stays
+ * valid, eval mode, no stream synchronisation. */
+int smaml_forecast_rollout(smaml_ctx* ctx, void* stream, const float* theta, int32_t task,
+                           const int32_t* origins_host, int32_t norig, int32_t batch, int32_t cycles, int32_t gap,
+                           const float* scale_host, float* traj, double* skill);
+
+/* Host-side counters of the last smaml_forecast_rollout call that passed its checks, summed over its passes; a
+ * "row" is one time step of one origin (N node rows): [0] cycles run, [1] rows whose GCN features the
+ * position-independent path computed (per origin (T - 1) + (R - 1) min(s, T - 1) with roll_reuse, R (T - 1)
+ * without), [2] rows through the t = 0 graph path (one per origin and cycle), [3] rows of layer-0 projection
+ * computed ([1] + [2]), [4] append launches. Writes min(cap, count) entries; *count = 5. Measurement and tests. */
+int smaml_rollout_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
 
 /* MC-dropout ensemble forecast: `members` (E, 1..64) stochastic forwards per window, in lockstep over the
  * member axis, with the ensemble mean, spread and probabilistic scores. Windows, passes, alignment and
@@ -513,6 +559,12 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *   "ens_group":                   smaml_forecast_ensemble runs its members this many at a time (0: all at
  *                                  once; at most 64; -1, the default: the largest group whose rings and
  *                                  per-member features fit 2 GiB; bitwise equal);
+ *   "roll_reuse":                  smaml_forecast_rollout computes GCN features and layer 0's projection only
+ *                                  for the rows the previous cycle appended (1) or for every row of every
+ *                                  window each cycle (0; bitwise equal). Default 1: at config-2 shapes, 32
+ *                                  origins x 15 cycles, 44.1 ms (44.0-44.4) against 54.0 ms (53.9-54.1) with 0,
+ *                                  outside both spreads (profiles/rollout_bench.log; a Python loop of
+ *                                  smaml_forecast calls per cycle: 53.9 ms);
  *   "adapt_group":                 smaml_adapt_steps_multi runs its regions this many at a time, each group
  *                                  as one set of launches per step (0: all at once; at most 64; -1, the
  *                                  default: the measured plan -- 3 to 5 regions in sets of 2, where a set

@@ -20,7 +20,17 @@ against the arm `deterministic`: smaml_forecast of the same windows at the same 
 whose median times E is the yardstick (E separate eval forecasts). p_lstm = 0.2 throughout. Optional
 --group G sets option ens_group for every ensemble arm.
 
+With --rollout R the tool times the autoregressive rollout (smaml_forecast_rollout) instead: --origins (32)
+origins, R cycles of Hf + 1 steps, one pass, the trajectory only, in three arms:
+  rollout           the library call as shipped (option roll_reuse at its default)
+  rollout_reuse_1/0 the option forced on / off (the A/B of keeping layer 0's projection across cycles)
+  python_loop       the way without the entry point: per cycle ctx.forecast() of every origin's current window
+                    and torch ops on the device that assemble the next windows (gap row, fed-back rows, exogenous
+                    channels) into a new stream for set_tasks
+and prints smaml_rollout_stats of the reuse arms and how far the loop's trajectory is from the library's.
+
 Usage: python tools/bench_forecast.py [--reps 5] [--warmup 1] [--windows 1200] [--members E [--batch 32] [--group G]]
+       python tools/bench_forecast.py --rollout 15 [--origins 32]
 """
 from __future__ import annotations
 
@@ -44,7 +54,11 @@ def main():
     p.add_argument("--members", type=int, default=0, help="time the E-member ensemble instead (see above)")
     p.add_argument("--batch", type=int, default=32, help="--members: windows per pass")
     p.add_argument("--group", type=int, default=-1, help="--members: option ens_group (-1: the default plan)")
+    p.add_argument("--rollout", type=int, default=0, help="time the R-cycle autoregressive rollout instead (see above)")
+    p.add_argument("--origins", type=int, default=32, help="--rollout: origins (one pass)")
     a = p.parse_args()
+    if a.rollout > 0:  # the stream holds every origin's R cycles and their targets
+        a.windows = a.origins + a.rollout * 9
     import torch
 
     from weatherforecast_stgcn_maml_amd import _capi, adapt, params, synth
@@ -71,6 +85,8 @@ def main():
         ctx.set_tasks([stream_t])
         return ctx
 
+    if a.rollout > 0:
+        return rollout_main(a, d, context, theta, stream_t, st, torch)
     if a.members > 0:
         return ensemble_main(a, d, context, theta, windows, st, torch)
     fc_ctx, ms_ctx = context(), context()
@@ -218,6 +234,100 @@ def ensemble_main(a, d, context, theta, windows, st, torch):
         "value": E * a.windows / (best["median_ms"] * 1e-3), "unit": "member-windows/s", "higher_is_better": True,
         "members": E, "windows": a.windows, "batch": B, "ens_group": a.group, "reps": a.reps, "warmup": a.warmup,
         "arms": res, "forecast_bytes": fbytes,
+        "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
+
+
+def rollout_main(a, d, context, theta, stream_t, st, torch):
+    R, B = a.rollout, a.origins
+    T, Hf, N, C = d.window_size, d.forecast_horizon, d.num_nodes, d.output_channels
+    s = Hf + 1
+    dev = theta.device
+    origins = list(range(B))
+    out, stats = {}, {}
+
+    def lib_arm(key, reuse):
+        ctx = context()
+        if reuse is not None:
+            ctx.set_option("roll_reuse", reuse)
+        traj = torch.zeros(B, R, s, N, C, device=dev)
+
+        def run():
+            ctx.forecast_rollout(st, theta, origins, B, R, 1, traj=traj)
+            torch.cuda.synchronize()
+            out[key] = traj
+            stats[key] = ctx.rollout_stats()
+        return run, ctx
+
+    lp_ctx = context()
+    wins = [i * T for i in range(B)]
+    pred = torch.zeros(B, N * Hf, C, device=dev)
+    traj_lp = torch.zeros(B, R, s, N, C, device=dev)
+
+    def loop_arm():
+        W = torch.stack([stream_t[o:o + T] for o in origins])  # [B, T, N, Cin]
+        for j in range(R):
+            lp_ctx.set_tasks([W.reshape(B * T, N, -1).contiguous()])
+            lp_ctx.forecast(st, theta, wins, B, pred=pred)
+            P = pred.view(B, Hf, N, C)  # the F4 view
+            gaprow = 0.5 * (W[:, T - 1, :, :C] + P[:, 0])
+            blk = torch.cat([gaprow[:, None], P], dim=1)
+            traj_lp[:, j] = blk
+            exo = torch.stack([stream_t[o + T + j * s:o + T + (j + 1) * s, :, C:] for o in origins])
+            W = torch.cat([W[:, s:], torch.cat([blk, exo], dim=-1)], dim=1)
+        torch.cuda.synchronize()
+        out["python_loop"] = traj_lp
+
+    arms = {"rollout": lib_arm("rollout", None), "rollout_reuse_1": lib_arm("rollout_reuse_1", 1),
+            "rollout_reuse_0": lib_arm("rollout_reuse_0", 0), "python_loop": (loop_arm, lp_ctx)}
+    times = {k: [] for k in arms}
+    for _ in range(a.warmup):
+        for fn, _ in arms.values():
+            fn()
+    for _ in range(a.reps):
+        for k, (fn, _) in arms.items():  # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    cats = {}
+    for k, (fn, ctx) in arms.items():
+        ctx.timing(True)
+        ctx.timing_collect()
+        fn()
+        cats[k] = {c: v for c, v in ctx.timing_collect().items() if v["launches"]}
+        ctx.timing(False)
+    ref = out["rollout"]
+    assert bool(torch.isfinite(ref).all())
+    assert torch.equal(out["rollout_reuse_1"], out["rollout_reuse_0"]) and torch.equal(out["rollout_reuse_1"], ref)
+    drift = float((out["python_loop"] - ref).norm() / ref.norm())
+    res = {}
+    for k, ts in times.items():
+        ms = np.asarray(ts) * 1e3
+        res[k] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+    print(f"{B} origins x {R} cycles of {s} steps (N = {N}, T = {T}), one pass, {a.reps} reps after {a.warmup} warm-up")
+    for k, r in res.items():
+        print(f"{k:16s} median {r['median_ms']:8.2f} ms  (min {r['min_ms']:.2f} - max {r['max_ms']:.2f})  "
+              f"{r['median_ms'] / R:.2f} ms per cycle")
+
+    def apart(x, y):
+        return x["max_ms"] < y["min_ms"] or y["max_ms"] < x["min_ms"]
+
+    on, off, lp = res["rollout_reuse_1"], res["rollout_reuse_0"], res["python_loop"]
+    print(f"roll_reuse 1 / roll_reuse 0 = {on['median_ms'] / off['median_ms']:.3f} "
+          f"(ranges {'do not overlap' if apart(on, off) else 'overlap'}); rollout / python_loop = "
+          f"{res['rollout']['median_ms'] / lp['median_ms']:.3f} (ranges "
+          f"{'do not overlap' if apart(res['rollout'], lp) else 'overlap'})")
+    for k in ("rollout_reuse_1", "rollout_reuse_0"):
+        print(f"smaml_rollout_stats {k}: {stats[k]}")
+    print(f"python_loop trajectory against the library's: rel-L2 {drift:.3g} (the loop's windows are not consecutive, "
+          f"so smaml_forecast forms layer 0's projection in its K loop: another rounding, fed back {R - 1} times)")
+    for k, c in cats.items():
+        print(f"{k} kernel ms by category: " + ", ".join(f"{n} {v['ms']:.1f} ({v['launches']})" for n, v in c.items()))
+    print(json.dumps({
+        "metric": f"{R}-cycle autoregressive rollout, origin-cycles/sec (N=441, T=24, config-2 dims, {B} origins)",
+        "value": B * R / (res["rollout"]["median_ms"] * 1e-3), "unit": "origin-cycles/s", "higher_is_better": True,
+        "origins": B, "cycles": R, "reps": a.reps, "warmup": a.warmup, "arms": res, "rollout_stats": stats,
+        "python_loop_rel_l2": drift,
         "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
 
 

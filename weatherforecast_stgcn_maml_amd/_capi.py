@@ -26,7 +26,7 @@ EXPORTS = (
     "smaml_dropout", "smaml_sync", "smaml_gcn_conv_ex", "smaml_gcn_conv_backward", "smaml_relu_mask",
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
     "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
-    "smaml_adapt_steps_full", "smaml_adapt_full_stats",
+    "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -130,6 +130,11 @@ _SIGS["smaml_adapt_steps_full"] = ([P, P, P, P, P, P, P, P, I32, I32, I32, PI32,
 _SIGS["smaml_adapt_full_stats"] = ([P, PI64, I32, PI32], I32)
 # smaml_adapt_full_stats order (launch counters of the last smaml_adapt_steps_full call)
 ADAPT_FULL_STATS = ("steps", "gcn_keep_fused", "gcn_keep_layer", "gcn_dz_fused", "gcn_dz_composed", "gcn_recompute")
+_SIGS["smaml_forecast_rollout"] = ([P, P, P, I32, PI32, I32, I32, I32, I32, PF32, P, P], I32)
+_SIGS["smaml_rollout_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_rollout_stats order (host counters of the last smaml_forecast_rollout call; a row = one time step of one origin)
+ROLLOUT_STATS = ("cycles", "gcn_rows", "graph_rows", "xg_rows", "append_launches")
+ROLLOUT_GAPS = {"persistence": 0, "midpoint": 1}  # smaml_forecast_rollout's gap argument
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
 
@@ -402,6 +407,31 @@ class Context:
             self._h, stream, ptr(theta), int(task), w.ctypes.data_as(PI32), w.size, int(batch), int(members),
             float(p_gcn), float(p_lstm), int(seed) & 0xFFFFFFFF, sc.ctypes.data_as(PF32) if sc is not None else None,
             opt(mean), opt(spread), opt(member_pred), opt(scores)))
+
+    def forecast_rollout(self, stream, theta, origins, batch, cycles, gap=1, task=0, scale=None, traj=None,
+                         skill=None):
+        """Autoregressive rollout of ``cycles`` cycles from the ``origins`` (window starts into task ``task``'s
+        stream) in passes of ``batch`` (smaml_forecast_rollout): ``traj`` [norig, cycles, Hf + 1, N, C] float32
+        and / or ``skill`` [3, cycles * (Hf + 1), C] float64 device tensors; ``gap`` 1 = midpoint, 0 =
+        persistence (``ROLLOUT_GAPS``); ``scale`` = per-variable factors of the skill sums, host, [C]."""
+        o = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+        if sc is not None and sc.size != self.dims.output_channels:
+            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        check(self._L.smaml_forecast_rollout(self._h, stream, ptr(theta), int(task), o.ctypes.data_as(PI32), o.size,
+                                             int(batch), int(cycles), int(gap),
+                                             sc.ctypes.data_as(PF32) if sc is not None else None,
+                                             ptr(traj) if traj is not None else None,
+                                             ptr(skill) if skill is not None else None))
+
+    def rollout_stats(self):
+        """{counter: count} of the last forecast_rollout call (host counters, no sync)."""
+        n = len(ROLLOUT_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_rollout_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(ROLLOUT_STATS)}
 
     def forecast_bytes(self):
         return int(self._L.smaml_forecast_bytes(self._h))

@@ -373,6 +373,15 @@ struct smaml_ctx {
   bool ens_lds_set = false; // k_ens_stats's dynamic-LDS limit raised on this context's device (ens_stats_prepare)
   int ens_share = 1;        // smaml_set_option("ens_share"): layer 0 of the LSTM once for all members (p_gcn = 0)
   int ens_group = -1;       // smaml_set_option("ens_group"): members per launch set (0: all; -1: ens_group_size)
+  // smaml_forecast_rollout shares fc_ring, fc_F (a run's features, time-major), fc_gcnA / B, fc_pred, fc_part
+  // and fc_scale, and adds the origins' private sequences, layer 0's projection slot table with the t = 0
+  // block behind it, the t = 0 rows' features and (no traj) one cycle's appended rows
+  HipBuf ro_seq;            // [B][T + (R - 1) s][N][Cin]
+  HipBuf ro_xg;             // [S + 1][M][4H]: slot rho % S of private row rho, then the t = 0 block
+  HipBuf ro_F0;             // [M][Hc]
+  HipBuf ro_blk;            // [B][s][N][C]
+  int roll_reuse = 1;       // smaml_set_option("roll_reuse"): only the appended rows get features and projection
+  int64_t ro_stats[5] = {}; // smaml_rollout_stats: counters of the last smaml_forecast_rollout call
   // side streams of the row-chunked BPTT (knob bptt_streams) and their fork / join events
   hipStream_t cs[4] = {};
   hipEvent_t fork_ev = nullptr, join_ev[4] = {};
@@ -2023,7 +2032,250 @@ int smaml_forecast(smaml_ctx* c, void* stream, const float* theta, int32_t task,
 int64_t smaml_forecast_bytes(const smaml_ctx* c) {
   if (!c) return 0;
   return c->fc_ring.cap + c->fc_F.cap + c->fc_gcnA.cap + c->fc_gcnB.cap + c->fc_xg.cap + c->fc_pred.cap +
-         c->fc_part.cap + c->fc_scale.cap + c->ens_ring.cap + c->ens_pred.cap;
+         c->fc_part.cap + c->fc_scale.cap + c->ens_ring.cap + c->ens_pred.cap + c->ro_seq.cap + c->ro_xg.cap +
+         c->ro_F0.cap + c->ro_blk.cap;
+}
+
+// ---- smaml_forecast_rollout: the forecast fed back in, cycle by cycle ------------------------------------
+namespace {
+// First private row whose features cycle j computes: with reuse only the rows the previous cycle appended
+// that the window's steps t >= 1 read (all of them when T > s; when T <= s the window holds fewer rows than a
+// cycle appends), else every row t >= 1 of the window. The run ends at row j s + T - 1.
+int roll_run_first(int j, int T, int sl, bool reuse) {
+  if (j == 0 || !reuse) return j * sl + 1;
+  return std::max(j * sl + 1, (j - 1) * sl + T);
+}
+
+struct RollPlan {
+  int R = 0, gap = 0, Bmax = 0, S = 0;
+  bool reuse = true, fused = false;
+  int64_t tab_src = 0, tab_cyc = 0;  // entries of the uploaded table: src[norig]; per cycle win[Bmax], run[Bmax]
+};
+
+// One pass of B origins (first of them `done` in the call's list) through the R cycles in lockstep.
+int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan& p, int64_t done, int B,
+                 const float* scale_dev, float* traj, double* skill) {
+  const Dims& d = c->d;
+  const int M = B * d.N, sl = d.Hf + 1, S = p.S;
+  const int64_t ring = infer_ring_floats(d, 1, M), blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H;
+  Work w{};
+  w.Z = 1;
+  w.B = B;
+  w.M = M;
+  w.F = c->fc_F.as<float>();
+  w.gcnA = c->fc_gcnA.as<float>();
+  w.gcnB = c->fc_gcnB.as<float>();
+  w.vcount = c->vcount;
+  w.kn = c->kn;
+  c->w = w;
+  TRY(prep_gate_images(c, s, theta, 0));
+  Work& cw = c->w;
+  const bool img = cw.gimg.th && cw.gimg_src == theta;
+  const char* gimg = img ? cw.gimg.th : nullptr;
+  const int64_t gimg_off = cw.gimg.off[0][0];
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
+  const int cin0 = c->po.lay[0].cin;
+  GcnWOff wo;
+  for (int k = 0; k < 4; ++k) {
+    wo.w[k] = c->go.w[k];
+    wo.b[k] = c->go.b[k];
+  }
+  if (p.fused) TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, c->gcn_wimg.as<char>()));
+  const float* const* src = nullptr;
+  TRY(xtab_at(c, p.tab_src + done, &src));
+  RollArgs ra{};
+  ra.seq = c->ro_seq.as<float>();
+  ra.seq_rows = d.T + (p.R - 1) * sl;
+  ra.seq_stride = (int64_t)ra.seq_rows * d.N * d.Cin0;
+  ra.src = src;
+  ra.B = B;
+  ra.N = d.N;
+  ra.Cin = d.Cin0;
+  ra.C = d.C;
+  ra.Hf = d.Hf;
+  ra.T = d.T;
+  TIMED(c, s, C_MISC, 0, launch_rollout_init(s, ra));
+  float* xg = c->ro_xg.as<float>();
+  float* xg0 = xg + (int64_t)S * slot;
+  float* F0 = c->ro_F0.as<float>();
+  float* Frun = c->fc_F.as<float>();
+  float* ringH = c->fc_ring.as<float>();
+  float* ringC = ringH + ring;
+  float* pred = c->fc_pred.as<float>();
+  float* bufs[2] = {cw.gcnA, cw.gcnB};
+  for (int j = 0; j < p.R; ++j) {
+    const float* const* wtab = nullptr;
+    const float* const* rtab = nullptr;
+    TRY(xtab_at(c, p.tab_cyc + (int64_t)j * 2 * p.Bmax, &wtab));
+    TRY(xtab_at(c, p.tab_cyc + ((int64_t)j * 2 + 1) * p.Bmax, &rtab));
+    // the rows t >= 1 this cycle owes: the four position-independent convs, then layer 0's projection into
+    // their slots (a run that wraps the table takes two launches)
+    const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
+    if (nrun > 0) {
+      if (p.fused) {
+        TIMED(c, s, C_GCN, 2.0 * B * nrun * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+              launch_gcn_mlp_run(s, d, B, nrun, rtab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
+      } else {
+        const float* from = nullptr;
+        for (int k = 0; k < 4; ++k) {
+          const bool last = k == 3;
+          float* dst = last ? Frun : bufs[k & 1];
+          TIMED(c, s, C_GCN, 2.0 * B * nrun * d.N * c->go.cin[k] * d.Hc,
+                launch_gcn_layer(s, d, k, B, B, k == 0 ? rtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
+                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, nrun * d.N, 0, nullptr));
+          from = dst;
+        }
+      }
+      for (int tau = 0; tau < nrun;) {
+        const int sl0 = (r0 + tau) % S, len = std::min(nrun - tau, S - sl0);
+        TIMED(c, s, C_XG, 2.0 * len * slot * cin0,
+              launch_xg_rows(s, d, cw, Frun + (int64_t)tau * M * d.Hc, (int64_t)len * M, theta, c->po, gimg, gimg_off,
+                             xg + (int64_t)sl0 * slot));
+        tau += len;
+      }
+      c->ro_stats[1] += (int64_t)B * nrun;
+      c->ro_stats[3] += (int64_t)B * nrun;
+    }
+    // the t = 0 rows aggregate over the graph (F3): per-layer chain over N-row blocks, as run_gcn's
+    const float* from = nullptr;
+    for (int k = 0; k < 4; ++k) {
+      const bool last = k == 3;
+      float* dst = last ? F0 : bufs[k & 1];
+      TIMED(c, s, C_GCN, 2.0 * M * c->go.cin[k] * d.Hc,
+            launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
+                             c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, d.N, d.N, nullptr, d.T * d.N));
+      from = dst;
+    }
+    TIMED(c, s, C_XG, 2.0 * slot * cin0, launch_xg_rows(s, d, cw, F0, M, theta, c->po, gimg, gimg_off, xg0));
+    c->ro_stats[2] += B;
+    c->ro_stats[3] += B;
+    XgDedup xd{};
+    xd.xg = xg;
+    xd.xg0 = xg0;
+    xd.src = theta;
+    xd.N = d.N;
+    xd.ring_S = S;
+    xd.ring_r0 = (j * sl) % S;
+    cw.xgd = xd;
+    for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+      FwdWave wv{};
+      double fl = fwd_wave(d, cw, c->po, diag, 0, false, wv);
+      for (int q = 0; q < wv.n; ++q)  // (the projection's flops are counted in C_XG)
+        if (wv.l[q] == 0) fl -= 2.0 * M * 4 * d.H * wv.lo[q].cin;
+      TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer(s, d, cw, diag, theta, 0, c->po, ringH, ringC));
+    }
+    TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
+          launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
+    float* out = traj ? traj + ((int64_t)done * p.R + j) * blkf : c->ro_blk.as<float>();
+    const int64_t ostride = traj ? (int64_t)p.R * blkf : blkf;
+    TIMED(c, s, C_MISC, 0, launch_rollout_append(s, ra, j, p.gap, j + 1 < p.R, pred, out, ostride));
+    c->ro_stats[4] += 1;
+    if (skill)
+      TIMED(c, s, C_MISC, 0,
+            launch_rollout_skill(s, ra, j, p.R, out, ostride, scale_dev, c->fc_part.as<float>(), skill, done == 0));
+    c->ro_stats[0] += 1;
+  }
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+}  // namespace
+
+int smaml_forecast_rollout(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* origins_host,
+                           int32_t norig, int32_t batch, int32_t cycles, int32_t gap, const float* scale_host,
+                           float* traj, double* skill) {
+  // (the checks that need no context first: they run without a device too)
+  if (!traj && !skill)
+    return fail(SMAML_EINVAL, "smaml_forecast_rollout: traj and skill are both NULL (nothing to compute)");
+  if (norig <= 0 || batch <= 0 || !origins_host)
+    return fail(SMAML_EINVAL, "smaml_forecast_rollout: norig and batch must be positive");
+  if (cycles <= 0) return fail(SMAML_EINVAL, "smaml_forecast_rollout: cycles must be positive");
+  if (gap != 0 && gap != 1)
+    return fail(SMAML_EINVAL, "smaml_forecast_rollout: gap must be 0 (persistence) or 1 (midpoint), got " +
+                                  std::to_string(gap));
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_forecast_rollout"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !aligned16(theta))
+    return fail(SMAML_EINVAL, "smaml_forecast_rollout: theta must be a 16-byte aligned device pointer");
+  if (task < 0 || task >= (int)c->feats.size())
+    return fail(SMAML_EINVAL, "smaml_forecast_rollout: task out of range");
+  const Dims& d = c->d;
+  const int sl = d.Hf + 1, R = cycles, Bmax = std::min(batch, norig);
+  if ((int64_t)d.T * Bmax * d.N * 4 * d.H >= (1ll << 30))
+    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^30");
+  // an origin needs every exogenous row its fed-back windows read; scoring also the last cycle's targets
+  const int64_t tt = c->t_total[task];
+  const int64_t need_in = d.T + (int64_t)(R - 1) * sl, need_sc = d.T + (int64_t)R * sl;
+  for (int i = 0; i < norig; ++i) {
+    const int64_t o = origins_host[i];
+    if (o < 0 || o + need_in > tt || (skill && o + need_sc > tt))
+      return fail(SMAML_EINVAL, "smaml_forecast_rollout: origin " + std::to_string(i) + " (start " + std::to_string(o) +
+                                    (skill && o >= 0 && o + need_in <= tt ? ") has no targets for " : ") does not fit ") +
+                                    std::to_string(R) + " cycles in the stream of " + std::to_string(tt) + " steps");
+  }
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  hipStream_t s = (hipStream_t)stream;
+  RollPlan p{};
+  p.R = R;
+  p.gap = gap;
+  p.Bmax = Bmax;
+  p.S = d.T;
+  p.reuse = c->roll_reuse != 0;
+  p.fused = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  // every buffer at the largest pass's size before the first launch, so no table entry can dangle
+  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = need_in, nrun_max = std::max(d.T - 1, 1);
+  const int64_t grows = p.fused ? Mx : nrun_max * Mx;
+  if (c->ro_seq.grow(Bmax * seq_rows * d.N * d.Cin0 * 4) != hipSuccess ||
+      c->ro_xg.grow((int64_t)(p.S + 1) * Mx * 4 * d.H * 4) != hipSuccess ||
+      c->ro_F0.grow(Mx * d.Hc * 4) != hipSuccess || c->fc_F.grow(nrun_max * Mx * d.Hc * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, grows * d.Hc * 4}, {&c->fc_gcnB, grows * d.Hc * 4}}) != hipSuccess ||
+      c->fc_ring.grow(2 * infer_ring_floats(d, 1, (int)Mx) * 4) != hipSuccess ||
+      c->fc_pred.grow(Mx * d.HfC * 4) != hipSuccess ||
+      (!traj && c->ro_blk.grow((int64_t)Bmax * sl * d.N * d.C * 4) != hipSuccess) ||
+      (skill && c->fc_part.grow((int64_t)rollout_skill_blocks(d, Bmax) * sl * d.C * 3 * 4) != hipSuccess) ||
+      (p.fused && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the rollout buffers failed (batch " + std::to_string(Bmax) + ", " +
+                                  std::to_string(R) + " cycles)");
+  const int64_t rowf = (int64_t)d.N * d.Cin0;
+  std::vector<const float*> ptrs((size_t)norig + (size_t)R * 2 * Bmax);
+  for (int i = 0; i < norig; ++i) ptrs[i] = c->feats[task] + (int64_t)origins_host[i] * rowf;
+  p.tab_src = 0;
+  p.tab_cyc = norig;
+  const float* seq = c->ro_seq.as<float>();
+  for (int j = 0; j < R; ++j)
+    for (int b = 0; b < Bmax; ++b) {
+      const float* sb = seq + (int64_t)b * seq_rows * rowf;
+      ptrs[(size_t)norig + ((size_t)j * 2) * Bmax + b] = sb + (int64_t)j * sl * rowf;
+      ptrs[(size_t)norig + ((size_t)j * 2 + 1) * Bmax + b] = sb + (int64_t)roll_run_first(j, d.T, sl, p.reuse) * rowf;
+    }
+  for (auto& x : c->ro_stats) x = 0;
+  const Work saved = c->w;
+  const int act = c->act_B;
+  auto run = [&]() -> int {
+    const float* scale_dev = nullptr;
+    if (skill && scale_host) {
+      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
+      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
+      scale_dev = c->fc_scale.as<float>();
+    }
+    TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
+    for (int64_t done = 0; done < norig; done += batch)
+      TRY(rollout_pass(c, s, theta, p, done, (int)std::min<int64_t>(batch, norig - done), scale_dev, traj, skill));
+    return SMAML_OK;
+  };
+  const int rc = run();
+  c->w = saved;
+  c->act_B = act;
+  return rc;
+}
+
+int smaml_rollout_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad rollout_stats arguments");
+  for (int i = 0; i < 5 && i < cap; ++i) counts[i] = c->ro_stats[i];
+  if (count) *count = 5;
+  return SMAML_OK;
 }
 
 int smaml_forecast_ensemble(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
@@ -2743,6 +2995,8 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->ad_phase_sync = (int)value;
   } else if (k == "adapt_group" && value >= -1 && value <= ADAPT_MAX_GROUP) {
     c->ad_group = (int)value;
+  } else if (k == "roll_reuse" && (value == 0 || value == 1)) {
+    c->roll_reuse = (int)value;
   } else if (k == "ens_share" && (value == 0 || value == 1)) {
     c->ens_share = (int)value;
   } else if (k == "ens_group" && value >= -1 && value <= 64) {

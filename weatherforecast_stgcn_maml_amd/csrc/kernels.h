@@ -219,6 +219,13 @@ struct XgDedup {
   const float* u_src = nullptr;
   int64_t zstride = 0;           // floats per task
   int N = 0;
+  // Second addressing mode (smaml_forecast_rollout, k_lstm_fwd_infer only; ring_S > 0, one task): xg is a
+  // slot table [ring_S][M][4H] in which private row rho of every origin of the pass lives in slot
+  // rho % ring_S, so step t >= 1 of the cycle whose window starts at private row ring_r0 reads the block of
+  // slot (ring_r0 + t) % ring_S, and step 0 reads xg0 [M][4H] (its features see the graph: recomputed per
+  // cycle). Both blocks are linear in the tile row m, as the consecutive-window mode's are.
+  const float* xg0 = nullptr;
+  int ring_S = 0, ring_r0 = 0;
 };
 __host__ __device__ inline int64_t xg_dedup_rows(int B, int T, int N) { return (int64_t)(2 * B + T - 2) * N; }
 // first row of step t's block of window rows in a task's XgDedup table (M = B N)
@@ -435,6 +442,38 @@ void launch_gcn_wsplit(hipStream_t s, const Dims& d, const float* gcn, const Gcn
 void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* const* xtab, const float* gcn,
                     const GcnWOff& wo, const char* img, float* F, const Drop* drop, bool dedup = false,
                     bool compact = false, float* keep_h = nullptr);
+// Row-run form of the fused stack (smaml_forecast_rollout): sample g < B contributes the `nrun` time steps
+// that start at xtab[g] ([nrun * N][Cin0], none of them a t = 0 row: no neighbours), and F is time-major
+// over the pass, F[(tau * B + g) * N + n] for tau < nrun. The per-row arithmetic is k_gcn_mlp's.
+void launch_gcn_mlp_run(hipStream_t s, const Dims& d, int B, int nrun, const float* const* xtab, const float* gcn,
+                        const GcnWOff& wo, const char* img, float* F);
+// k_xg_dedup over `rows` plain rows F [rows][cin] of one task: out [rows][4H] (the rollout's slot blocks)
+void launch_xg_rows(hipStream_t s, const Dims& d, const Work& w, const float* F, int64_t rows, const float* params,
+                    const ParamOff& po, const char* img, int64_t img_off, float* out);
+// ---- autoregressive rollout (smaml_forecast_rollout; kernels.hip) ----
+// Per-pass addressing of the rollout kernels: origin b's private sequence seq + b * seq_stride, rows
+// [seq_rows][N][Cin]; its stream rows from src[b] = stream + o_b * N * Cin.
+struct RollArgs {
+  float* seq = nullptr;
+  int64_t seq_stride = 0;            // floats between two origins' sequences
+  const float* const* src = nullptr; // [B]
+  int B = 0, N = 0, Cin = 0, C = 0, Hf = 0, T = 0;
+  int seq_rows = 0;                  // T + (R - 1)(Hf + 1)
+};
+// seq[b][rho] = src[b][rho] for rho < T (all channels)
+void launch_rollout_init(hipStream_t s, const RollArgs& a);
+// Cycle j's appended rows from pred [B][N*Hf][C] (F4 view [Hf][N][C]): the s = Hf + 1 rows at rho0 = j s + T
+// (gap row, then the Hf predicted rows; channels >= C from the stream row of the same time) into the
+// sequences when `store_seq` (not on the last cycle: nothing reads them), and their weather channels into
+// out + b * out_stride [s][N][C] (the cycle's traj block, or a scratch the skill sums read).
+void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, bool store_seq, const float* pred,
+                           float* out, int64_t out_stride);
+// Skill sums of cycle j's s leads from blk + b * blk_stride [s][N][C]: f32 partials per block into part
+// [rollout_skill_blocks][s C][3], added in double onto skill [3][R s][C] at leads j s .. j s + s - 1 (first:
+// overwritten). launch_skill_sums's scheme: fixed order, no atomics.
+int rollout_skill_blocks(const Dims& d, int B);
+void launch_rollout_skill(hipStream_t s, const RollArgs& a, int j, int R, const float* blk, int64_t blk_stride,
+                          const float* scale, float* part, double* skill, bool first);
 // out[z] = layer-0 input projection of every distinct stream row of task z's consecutive windows
 // (XgDedup layout) with the gate weights W_ih0 of `params` (theta or the tangent direction U); the
 // weights come from the pre-split images `img` when given (w.gimg.th / .u), else from `params`; F is

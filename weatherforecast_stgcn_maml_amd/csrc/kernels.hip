@@ -571,6 +571,8 @@ __global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_infer
   // XG: layer 0's input projection comes from the XgDedup table (added in the epilogue, as in lstm_fwd_step),
   // the K loop starts past the input segment and F (which may be compact) is not read
   const float* xgt = xd.xg && l == 0 ? xd.xg + (int64_t)z * xd.zstride + xg_dedup_row0(t, M, xd.N) * (4 * H) : nullptr;
+  // slot-table mode (XgDedup::ring_S, the rollout): only the base of step t's block differs
+  if (xgt && xd.ring_S > 0) xgt = t == 0 ? xd.xg0 : xd.xg + (int64_t)((xd.ring_r0 + t) % xd.ring_S) * M * (4 * H);
   const int kbeg = xgt ? cin : 0;
   const float* X = l > 0 ? at(ringH, l - 1, t) : xgt ? F : F + ((int64_t)z * T + t) * M * cin;
   const SegKCt<2> la{{X, Hp}, {cin, H}, M};
@@ -727,6 +729,25 @@ void launch_xg_dedup(hipStream_t s, const Dims& d, const Work& w, const float* p
   } else {
     SMAML_DISPATCH_H(d.H, (k_xg_dedup<HT, false><<<grid, CfgGate::NTH, 0, s>>>(
                               w.F, fz, a, params + po.lay[0].wih, tstride, nullptr, 0, out, w.xgd.zstride)));
+  }
+}
+
+// k_xg_dedup over plain rows (XgRowsA's compact form: row r of F is operand row r): the rollout's projection
+// of a run of private rows, F and out both time-major over the pass.
+void launch_xg_rows(hipStream_t s, const Dims& d, const Work& w, const float* F, int64_t rows, const float* params,
+                    const ParamOff& po, const char* img, int64_t img_off, float* out) {
+  if (rows <= 0) return;
+  const int ntm = (int)((rows + CfgGate::BM - 1) / CfgGate::BM);
+  const int ngrp = (d.H + 32 * CfgGate::WAVES_N - 1) / (32 * CfgGate::WAVES_N);
+  dim3 grid(gate_blocks(ntm, ngrp), 1, 1);
+  const int cin = po.lay[0].cin;
+  const XgRowsA a{nullptr, (int)rows, d.N, d.T, cin, (int)rows, FastDiv((uint32_t)d.N), 1};
+  count_variant(w, V_XG_DEDUP);
+  if (img) {
+    SMAML_DISPATCH_H(d.H, (k_xg_dedup<HT, true><<<grid, CfgGate::NTH, 0, s>>>(F, 0, a, nullptr, 0, img + img_off, 0, out, 0)));
+  } else {
+    SMAML_DISPATCH_H(d.H, (k_xg_dedup<HT, false><<<grid, CfgGate::NTH, 0, s>>>(F, 0, a, params + po.lay[0].wih, 0,
+                                                                              nullptr, 0, out, 0)));
   }
 }
 
@@ -1486,6 +1507,121 @@ void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, c
   const int nblk = skill_blocks(d, B);
   k_skill_part<<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part);
   k_skill_final<<<(3 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, skill, first ? 1 : 0);
+}
+
+// ---- autoregressive rollout (smaml_forecast_rollout) ------------------------------------------------
+// Origin b (blockIdx.y) keeps a private sequence X = a.seq + b a.seq_stride, rows [seq_rows][N][Cin]; its
+// stream rows are a.src[b] = S + o_b N Cin, so S[o_b + rho] is row rho of a.src[b].
+__global__ void k_rollout_init(RollArgs a) {
+  const int b = blockIdx.y;
+  const int64_t n4 = (int64_t)a.T * a.N * a.Cin / 4;  // (Cin % 4 == 0, both 16-byte aligned)
+  const float4* src = reinterpret_cast<const float4*>(a.src[b]);
+  float4* dst = reinterpret_cast<float4*>(a.seq + (int64_t)b * a.seq_stride);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = src[i];
+}
+
+void launch_rollout_init(hipStream_t s, const RollArgs& a) {
+  const int64_t n4 = (int64_t)a.T * a.N * a.Cin / 4;
+  const unsigned gx = (unsigned)std::min<int64_t>((n4 + 255) / 256, 256);
+  k_rollout_init<<<dim3(gx, (unsigned)a.B), 256, 0, s>>>(a);
+}
+
+// One thread per element (i, n, c) of the cycle's s = Hf + 1 appended rows, rho = rho0 + i, rho0 = j s + T:
+//   c >= C: the exogenous channel of the stream row of the same absolute time, S[o + rho][n][c];
+//   i == 0: the gap row no forecast covers (F5): X[rho0 - 1][n][c] held (gap 0) or its f32 midpoint with the
+//           first predicted row, 0.5f * (X[rho0 - 1][n][c] + P[0][n][c]) (gap 1);
+//   i >= 1: P[i - 1][n][c], P = the flat prediction [N Hf][C] of origin b read as [Hf][N][C] (F4): a copy.
+// Row rho0 - 1 was written by the previous cycle (or is an observed row): no thread of this launch writes it.
+// The weather channels of stream rows >= o + T are never read. Plain 4-byte accesses: C need not be a
+// multiple of 4.
+__global__ void k_rollout_append(RollArgs a, int rho0, int gap, int store_seq, const float* __restrict__ pred,
+                                 float* __restrict__ out, int64_t out_stride) {
+  const int b = blockIdx.y, s = a.Hf + 1;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)s * a.N * a.Cin) return;
+  const int c = (int)(e % a.Cin);
+  const int64_t in = e / a.Cin;
+  const int n = (int)(in % a.N), i = (int)(in / a.N);
+  float* X = a.seq + (int64_t)b * a.seq_stride;
+  const int64_t at = ((int64_t)(rho0 + i) * a.N + n) * a.Cin + c;
+  if (c >= a.C) {
+    if (store_seq) X[at] = a.src[b][at];
+    return;
+  }
+  const float* P = pred + (int64_t)b * a.N * a.Hf * a.C;
+  float v;
+  if (i == 0) {
+    const float prev = X[((int64_t)(rho0 - 1) * a.N + n) * a.Cin + c];
+    v = gap ? 0.5f * (prev + P[(int64_t)n * a.C + c]) : prev;
+  } else {
+    v = P[((int64_t)(i - 1) * a.N + n) * a.C + c];
+  }
+  if (store_seq) X[at] = v;
+  out[(int64_t)b * out_stride + ((int64_t)i * a.N + n) * a.C + c] = v;
+}
+
+void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, bool store_seq, const float* pred,
+                           float* out, int64_t out_stride) {
+  const int64_t n = (int64_t)(a.Hf + 1) * a.N * a.Cin;
+  k_rollout_append<<<dim3((unsigned)((n + 255) / 256), (unsigned)a.B), 256, 0, s>>>(
+      a, j * (a.Hf + 1) + a.T, gap, store_seq ? 1 : 0, pred, out, out_stride);
+}
+
+// Skill sums of one cycle: k_skill_part's scheme per (row i of the cycle, variable c) -- block (i C + c, k)
+// sums the (origin, node) pairs [k SKILL_PAIRS, (k + 1) SKILL_PAIRS) in f32, k_rollout_skill_final adds the
+// blocks in order in double onto the absolute lead j s + i of skill [3][R s][C]. x = the cycle's block row
+// (gap row included), y = S[o + T + j s + i][n][c], y_last = S[o + T - 1][n][c].
+__global__ __launch_bounds__(NT) void k_rollout_skill_part(RollArgs a, int k0, const float* __restrict__ blk,
+                                                           int64_t blk_stride, const float* __restrict__ scale,
+                                                           float* __restrict__ part) {
+  __shared__ float red[NT / 64];
+  const int ic = blockIdx.x, i = ic / a.C, c = ic - i * a.C;
+  const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, a.B * a.N);
+  const float sc = scale ? scale[c] : 1.f;
+  float se = 0.f, ae = 0.f, pe = 0.f;
+  for (int p = p0 + (int)threadIdx.x; p < p1; p += NT) {
+    const int b = p / a.N, n = p - b * a.N;
+    const float* xs = a.src[b];
+    const float y = xs[((int64_t)(a.T + k0 + i) * a.N + n) * a.Cin + c];
+    const float yl = xs[((int64_t)(a.T - 1) * a.N + n) * a.Cin + c];
+    const float x = blk[(int64_t)b * blk_stride + ((int64_t)i * a.N + n) * a.C + c];
+    const float e = sc * (x - y), q = sc * (yl - y);
+    se = fmaf(e, e, se);
+    ae += fabsf(e);
+    pe = fmaf(q, q, pe);
+  }
+  float* o = part + ((int64_t)blockIdx.y * gridDim.x + ic) * 3;
+  const float s0 = block_sum(se, red);
+  const float s1 = block_sum(ae, red);
+  const float s2 = block_sum(pe, red);
+  if (threadIdx.x == 0) {
+    o[0] = s0;
+    o[1] = s1;
+    o[2] = s2;
+  }
+}
+
+__global__ void k_rollout_skill_final(const float* __restrict__ part, int nblk, int sC, int k0C, int64_t RsC,
+                                      double* __restrict__ skill, int first) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 3 * sC) return;
+  const int k = i / sC, ic = i - k * sC;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += (double)part[((int64_t)b * sC + ic) * 3 + k];
+  double* o = skill + (int64_t)k * RsC + k0C + ic;
+  *o = first ? s : *o + s;
+}
+
+int rollout_skill_blocks(const Dims& d, int B) { return skill_blocks(d, B); }
+
+void launch_rollout_skill(hipStream_t s, const RollArgs& a, int j, int R, const float* blk, int64_t blk_stride,
+                          const float* scale, float* part, double* skill, bool first) {
+  const int sl = a.Hf + 1, sC = sl * a.C;
+  const int nblk = (a.B * a.N + SKILL_PAIRS - 1) / SKILL_PAIRS;
+  k_rollout_skill_part<<<dim3(sC, nblk), NT, 0, s>>>(a, j * sl, blk, blk_stride, scale, part);
+  k_rollout_skill_final<<<(3 * sC + 127) / 128, 128, 0, s>>>(part, nblk, sC, j * sC, (int64_t)R * sC, skill,
+                                                            first ? 1 : 0);
 }
 
 // ---- ensemble statistics (smaml_forecast_ensemble) --------------------------------------------------

@@ -91,7 +91,9 @@ typedef __attribute__((address_space(1))) const void gm_gbl_t;
 // store their outputs (post-ReLU, post-dropout: the next layer's operand) to a.h[layer], per sample
 // [g][T*N][HC] at row q -- the layout the GCN backward reads -- with the F store's float4-per-lane pattern.
 // Never with dedup (every sample keeps its own rows). The arithmetic, and so F, is the plain kernel's.
-template <int HC, bool KEEP = false>
+// RUN (smaml_forecast_rollout): sample g's rows are the a.rows1 = nrun N rows at a.xtab[g] (no t = 0 row among
+// them), row q = tau N + n of it goes to F[(tau B + g) N + n] -- time-major over the pass. Same arithmetic.
+template <int HC, bool KEEP = false, bool RUN = false>
 __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
   constexpr int NT = HC / 32;  // channel tiles
   constexpr int SB = gm_step_bytes(HC);
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
   const bool valid = r1 < a.R1;
   const uint32_t rr = valid ? (uint32_t)r1 : 0u;
   const int g = (int)a.rows_div.div(rr);
-  const int q = a.N + (int)(rr - (uint32_t)g * (uint32_t)a.rows1);
+  const int q = (RUN ? 0 : a.N) + (int)(rr - (uint32_t)g * (uint32_t)a.rows1);
   const int z = a.dedup ? g : (int)a.b_div.div((uint32_t)g), s = a.dedup ? 0 : g - z * a.B;
   const int t = (int)a.n_div.div((uint32_t)q), n = q - t * a.N;
   const float* xrow = a.xtab[a.dedup ? g * a.B : g] + (int64_t)q * a.cin0;
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
   const int t_lo = a.dedup ? max(1, t - (a.B - 1)) : t, t_hi = a.dedup ? min(a.T - 1, t) : t;
   const int boff = s + t;
   float* frow = a.F + (((int64_t)z * a.T) * a.M + n) * HC;
-  if (a.compact) {  // once, at compact row M + (t - 1) N + n (t = the stream row here): tt = t_lo only
+  if constexpr (RUN) frow = a.F + ((int64_t)t * a.M + (int64_t)g * a.N + n) * HC;
+  if (!RUN && a.compact) {  // once, at compact row M + (t - 1) N + n (t = the stream row here): tt = t_lo only
     frow = a.F + (((int64_t)z * a.T) * a.M + a.M + (int64_t)(t - 1) * a.N + n) * HC;
   }
   float* hrow = nullptr;  // KEEP: this lane's row of h[0]
@@ -226,8 +229,9 @@ __global__ __launch_bounds__(64 * GM_WAVES) void k_gcn_mlp(GcnMlpArgs a) {
     epilogue(layer);
   }
   if (valid) {
-    for (int tt = t_lo; tt <= (a.compact ? t_lo : t_hi); ++tt) {
-      float* fr = a.compact ? frow : frow + ((int64_t)tt * a.M + (int64_t)(boff - tt) * a.N) * HC;
+    const bool once = RUN || a.compact;
+    for (int tt = t_lo; tt <= (once ? t_lo : t_hi); ++tt) {
+      float* fr = once ? frow : frow + ((int64_t)tt * a.M + (int64_t)(boff - tt) * a.N) * HC;
 #pragma unroll
       for (int ci = 0; ci < NT; ++ci)
 #pragma unroll
@@ -313,6 +317,29 @@ void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* co
     k_gcn_mlp<256, true><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
   else
     k_gcn_mlp<256><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
+}
+
+void launch_gcn_mlp_run(hipStream_t s, const Dims& d, int B, int nrun, const float* const* xtab, const float* gcn,
+                        const GcnWOff& wo, const char* img, float* F) {
+  if (nrun <= 0) return;
+  GcnMlpArgs a{};
+  a.xtab = xtab;
+  a.gcn = gcn;
+  a.wo = wo;
+  a.wimg = img;
+  a.F = F;
+  a.rows1 = nrun * d.N;
+  a.R1 = (int64_t)B * a.rows1;
+  a.rows_div = FastDiv((uint32_t)a.rows1);
+  a.b_div = FastDiv((uint32_t)B);
+  a.n_div = FastDiv((uint32_t)d.N);
+  a.N = d.N;
+  a.T = nrun;
+  a.B = B;
+  a.M = (int64_t)B * d.N;
+  a.cin0 = d.Cin0;
+  const unsigned blocks = (unsigned)((a.R1 + GM_ROWS - 1) / GM_ROWS);
+  k_gcn_mlp<256, false, true><<<blocks, 64 * GM_WAVES, 0, s>>>(a);
 }
 
 }  // namespace smaml

@@ -143,8 +143,179 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
     return ForecastResult(out, rmse, mae, prmse, skill, int(w.size), w)
 
 
+# ---- autoregressive rollout (smaml_forecast_rollout) ----------------------------------------------------
+# The model predicts Hf steps; feeding the forecast back in reaches day-scale leads. Stride s = Hf + 1: the
+# targets of a window skip t + 0 (dataset.py:40-48), so each cycle appends a gap row no forecast
+# covers, then the Hf predicted rows. The first C input channels are the predicted variables (dataset.py:
+# targets are stream[..., :C]); the others are calendar / Koppen features known in advance and are taken
+# from the stream row of the same absolute time.
+GAPS = {"persistence": 0, "midpoint": 1}
+
+
+def _gap_code(gap) -> int:
+    if isinstance(gap, str):
+        if gap not in GAPS:
+            raise ValueError(f"gap must be one of {sorted(GAPS)} (or 0 / 1), got {gap!r}")
+        return GAPS[gap]
+    if int(gap) not in (0, 1):
+        raise ValueError(f"gap must be 0 (persistence) or 1 (midpoint), got {gap!r}")
+    return int(gap)
+
+
+def rollout_origins(t_total: int, window: int, horizon: int, cycles: int, score: bool) -> np.ndarray:
+    """Every origin the range rule of ``smaml_forecast_rollout`` admits: ``o + T + (R-1) s <= t_total``, with
+    ``score`` ``o + T + R s <= t_total`` (``s = Hf + 1``). ``cycles = 1`` gives ``default_windows``."""
+    s, R = horizon + 1, int(cycles)
+    if R < 1:
+        raise ValueError(f"cycles must be >= 1, got {cycles}")
+    n = t_total - window - (R if score else R - 1) * s + 1
+    return np.arange(max(0, n), dtype=np.int32)
+
+
+def extend_stream(features, exo) -> np.ndarray:
+    """``features [t, N, Cin]`` followed by ``len(exo)`` rows past the last observation: their exogenous
+    channels are ``exo [k, N, Cin - C]`` (C is inferred from its width), their weather channels NaN -- the
+    rollout never reads those as inputs. For forecasting past the end of the observations (``score=False``)."""
+    f = np.asarray(features.detach().cpu() if hasattr(features, "detach") else features, np.float32)
+    e = np.asarray(exo.detach().cpu() if hasattr(exo, "detach") else exo, np.float32)
+    if f.ndim != 3 or e.ndim != 3 or e.shape[1] != f.shape[1] or not 0 < e.shape[2] <= f.shape[2]:
+        raise ValueError(f"exo {e.shape} does not extend features {f.shape}: want [k, N, Cin - C]")
+    C = f.shape[2] - e.shape[2]
+    tail = np.full((e.shape[0],) + f.shape[1:], np.nan, np.float32)
+    tail[:, :, C:] = e
+    return np.concatenate([f, tail], axis=0)
+
+
+def rollout_reference(forward, features, origins: Sequence[int], dims, cycles: int, gap="midpoint") -> np.ndarray:
+    """The definition of ``smaml_forecast_rollout`` in numpy: ``traj [norig, R s, N, C]`` (float32,
+    normalised) of the origins ``origins`` of ``features [t_total, N, Cin]``, with ``forward`` a callable
+    ``window [T*N, Cin] -> [N*Hf, C]`` (the model's eval-mode output, flat rows as the model writes them).
+
+    Per origin ``o`` a private sequence ``X[rho] = S[o + rho]``, ``rho < T``; cycle ``j`` runs the window
+    ``X[j s : j s + T]``, reads the flat output as ``P [Hf, N, C]`` (F4), and appends at ``rho0 = j s + T`` the
+    gap row (``X[rho0 - 1]`` held, or its float32 midpoint with ``P[0]``) and ``P``; the channels ``>= C`` of
+    appended rows are those of ``S[o + rho]``. Weather channels of stream rows ``>= o + T`` are never read."""
+    T, Hf, N, C = dims.window_size, dims.forecast_horizon, dims.num_nodes, dims.output_channels
+    s, R, g = Hf + 1, int(cycles), _gap_code(gap)
+    if R < 1:
+        raise ValueError(f"cycles must be >= 1, got {cycles}")
+    f = np.asarray(features)
+    rows = T + (R - 1) * s
+    out = np.empty((len(origins), R * s, N, C), np.float32)
+    for i, o in enumerate(origins):
+        o = int(o)
+        if o < 0 or o + rows > f.shape[0]:
+            raise ValueError(f"origin {o} does not fit {R} cycles in a stream of {f.shape[0]} steps")
+        X = np.zeros((rows, N, f.shape[2]), np.float32)
+        X[:T] = f[o:o + T]
+        X[T:, :, C:] = f[o + T:o + rows, :, C:]
+        for j in range(R):
+            P = np.asarray(forward(X[j * s:j * s + T].reshape(T * N, -1)), np.float32).reshape(Hf, N, C)
+            prev = X[j * s + T - 1, :, :C]
+            first = np.float32(0.5) * (prev + P[0]) if g else prev
+            blk = np.concatenate([first[None].astype(np.float32), P], axis=0)
+            out[i, j * s:(j + 1) * s] = blk
+            if j + 1 < R:
+                X[j * s + T:(j + 1) * s + T, :, :C] = blk
+    return out
+
+
+def rollout_skill_reference(traj, features, origins: Sequence[int], dims, scale=None) -> np.ndarray:
+    """The three sums ``[3, R s, C]`` (float64; order ``SUMS``) of a normalised trajectory ``traj
+    [norig, R s, N, C]`` per absolute lead ``k`` and variable, over origins and nodes: every row (gap rows
+    included) against ``y = features[o + T + k]``, and the persistence ``y_last = features[o + T - 1]``."""
+    T, N, C = dims.window_size, dims.num_nodes, dims.output_channels
+    x = np.asarray(traj, np.float64)
+    x = x.reshape(len(origins), -1, N, C)
+    K = x.shape[1]
+    f = np.asarray(features)
+    sc = np.ones(C) if scale is None else np.asarray(scale, np.float64).reshape(C)
+    out = np.zeros((3, K, C))
+    for xi, o in zip(x, origins):
+        o = int(o)
+        if o < 0 or o + T + K > f.shape[0]:
+            raise ValueError(f"origin {o} has no targets for {K} leads in a stream of {f.shape[0]} steps")
+        y = f[o + T:o + T + K, :, :C].astype(np.float64)
+        y_last = f[o + T - 1, :, :C].astype(np.float64)[None]
+        e = (xi - y) * sc
+        q = (y_last - y) * sc
+        out[0] += (e * e).sum(axis=1)
+        out[1] += np.abs(e).sum(axis=1)
+        out[2] += (q * q).sum(axis=1)
+    return out
+
+
+@dataclass
+class RolloutResult:
+    traj: Optional[np.ndarray]              # [norig, R s, N, C], physical units over the first len(std) variables
+    is_gap: np.ndarray                      # [R s] bool: the rows no forecast covers (filled by the gap rule)
+    rmse: Optional[np.ndarray]              # [R s, C] per absolute lead (hours on an hourly stream: k + 1 ahead)
+    mae: Optional[np.ndarray]               # [R s, C]
+    persistence_rmse: Optional[np.ndarray]  # [R s, C]
+    skill: Optional[np.ndarray]             # [R s, C]: 1 - SSE / SSE_persistence
+    n_origins: int
+    origins: np.ndarray
+    cycles: int
+    gap: str
+
+
+def rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, gap="midpoint", batch: int = 32,
+            score: bool = True, ctx=None) -> RolloutResult:
+    """Autoregressive forecast of ``cycles`` x ``(Hf + 1)`` steps from every origin (``smaml_forecast_rollout``):
+    each cycle's prediction is fed back as the weather channels of the next window, the exogenous channels
+    come from ``features`` (use ``extend_stream`` to forecast past the last observation, with ``score=False``).
+    Arguments as ``forecast``; ``origins`` defaults to ``rollout_origins``; ``gap``: "midpoint" or
+    "persistence" fills the row between a window and its first target. Returns the trajectory in physical
+    units and, with ``score``, RMSE / MAE / persistence RMSE / skill per absolute lead and variable (count per
+    lead: ``norig * N``)."""
+    import torch
+
+    from . import _capi
+    from .model import _set_graph
+
+    g = _gap_code(gap)
+    R = int(cycles)
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _capi.SmamlError(-1, "rollout runs on a HIP device only")
+    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
+    f = f.to(dev, torch.float32).contiguous()
+    T = model.base_stgcn.window_size
+    Hf, C = model.forecast_horizon, model.out_channels
+    s = Hf + 1
+    t_total, N = int(f.shape[0]), int(f.shape[1])
+    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
+    is_gap = (np.arange(R * s) % s) == 0
+    gname = "midpoint" if g else "persistence"
+    if o.size == 0:
+        return RolloutResult(None, is_gap, None, None, None, None, 0, o, R, gname)
+    if ctx is None:
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+    else:
+        dims = model.dims(N)
+        _set_graph(ctx, ei)
+        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
+        ctx.set_gcn_params(gflat)
+        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
+    ctx.set_tasks([f])
+    mean, std = _stats(stats, C)
+    traj = torch.empty(o.size, R, s, N, C, device=dev)
+    sums = torch.empty(3, R * s, C, device=dev, dtype=torch.float64) if score else None
+    with torch.no_grad():
+        ctx.forecast_rollout(_capi.stream_ptr(torch), theta, o, batch, R, g, scale=std if score else None, traj=traj,
+                             skill=sums)
+        scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
+        shift_t = torch.from_numpy(mean.astype(np.float32)).to(dev)
+        out = (traj * scale_t + shift_t).view(o.size, R * s, N, C).cpu().numpy()
+    if not score:
+        return RolloutResult(out, is_gap, None, None, None, None, int(o.size), o, R, gname)
+    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), int(o.size) * N)
+    return RolloutResult(out, is_gap, rmse, mae, prmse, skill, int(o.size), o, R, gname)
+
+
 # ---- MC-dropout ensemble (smaml_forecast_ensemble) -----------------------------------------------------
-ENSEMBLE_SUMS = ("mean_sse", "variance", "crps", "persistence_sse")  # order of smaml_forecast_ensemble's scores
+ENSEMBLE_SUMS =("mean_sse", "variance", "crps", "persistence_sse")  # order of smaml_forecast_ensemble's scores
 
 
 def ensemble_reference(member_pred, features, windows: Sequence[int], dims, scale=None):
