@@ -79,7 +79,10 @@ int smaml_param_layout(const smaml_dims* dims, int32_t which, int64_t* offsets, 
 
 /* Normalised t=0 adjacency of PyG gcn_norm as ELL (width 8): replaces the
  * add_remaining_self_loops + degree + norm part of GCNConv (model.py:23-26) for the
- * edge_index of graphBuilder.build_spatial_graph (graphBuilder.py:9-47). */
+ * edge_index of graphBuilder.build_spatial_graph (graphBuilder.py:9-47). Any edge_index with
+ * in-degree <= 7 (self loops not counted) is accepted: parallel edges count twice, self loops in the
+ * input are replaced by the one every node gets, isolated nodes keep that loop alone (weight 1), the
+ * edge order is free. A source or target outside [0, num_nodes) or an in-degree of 8: SMAML_EINVAL. */
 int smaml_graph_ell(const int64_t* edge_index_host, int64_t num_edges, int32_t num_nodes,
                     int32_t* cols_host, float* vals_host);
 
@@ -119,13 +122,18 @@ int smaml_set_task_ids(smaml_ctx* ctx, const int32_t* ids_host, int32_t n);
 /* ---- forward (module API) ----------------------------------------------------------- */
 
 /* GCNConv.forward(x, edge_index) (PyG semantics, F3): x [rows, cin] -> out [rows, cout].
- * Rows < num_nodes aggregate over the graph, the rest see only their self loop. */
+ * Rows < num_nodes aggregate over the graph, the rest see only their self loop.
+ * Short inputs: rows < num_nodes is SMAML_EINVAL ("rows ... must be at least num_nodes"), checked before
+ * anything is launched -- row q < num_nodes gathers any of rows 0 .. num_nodes - 1 of x, so a shorter x would
+ * be read past its end (PyG raises an IndexError there). */
 int smaml_gcn_conv(smaml_ctx* ctx, void* stream, const float* x, int32_t rows, int32_t cin,
                    const float* weight, const float* bias, int32_t cout, float* out);
 
 /* GCNConv / Linear forward and backward for the module API's autograd (model.py:7-52: STGCN trained on
  * its own; the hybrid path keeps the GCN frozen, F2). flags: SMAML_GCN_RELU applies ReLU to the output,
- * SMAML_GCN_PLAIN skips the graph aggregation (a plain x W^T + b, e.g. STGCN.output_layer). */
+ * SMAML_GCN_PLAIN skips the graph aggregation (a plain x W^T + b, e.g. STGCN.output_layer).
+ * Short inputs: without SMAML_GCN_PLAIN, rows < num_nodes is SMAML_EINVAL as in smaml_gcn_conv (nothing is
+ * launched); with it any rows > 0 are accepted, since no row is gathered. */
 #define SMAML_GCN_RELU 1
 #define SMAML_GCN_PLAIN 2
 int smaml_gcn_conv_ex(smaml_ctx* ctx, void* stream, const float* x, int32_t rows, int32_t cin,
@@ -133,7 +141,9 @@ int smaml_gcn_conv_ex(smaml_ctx* ctx, void* stream, const float* x, int32_t rows
 
 /* Backward of z = A_hat x W^T + b (SMAML_GCN_PLAIN: A_hat = I) given dz = dL/dz [rows][cout]:
  * dx = A_hat^T dz W [rows][cin] (optional), dwb = [dL/dW (cout x cin, row-major) | dL/db (cout)]
- * (optional). Deterministic (fixed-order sums). Replaces autograd through PyG GCNConv / nn.Linear. */
+ * (optional). Deterministic (fixed-order sums). Replaces autograd through PyG GCNConv / nn.Linear.
+ * Short inputs: without SMAML_GCN_PLAIN, rows < num_nodes is SMAML_EINVAL as in smaml_gcn_conv (both the
+ * A_hat x of dW and the A_hat^T dz of dx gather rows 0 .. num_nodes - 1); nothing is launched or reserved. */
 int smaml_gcn_conv_backward(smaml_ctx* ctx, void* stream, const float* x, int32_t rows, int32_t cin,
                             const float* weight, int32_t cout, const float* dz, int32_t flags, float* dx, float* dwb);
 

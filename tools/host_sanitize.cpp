@@ -358,6 +358,35 @@ int main() {
   for (int k = 1; k <= 8; ++k) star.push_back(k);
   for (int k = 1; k <= 8; ++k) star.push_back(0);
   CHECK(smaml_graph_ell(star.data(), 8, N, cols.data(), vals.data()) == SMAML_EINVAL);
+  // an irregular multigraph on 6 nodes, edges in no order: node 0 with 7 in-edges (the edge 1 -> 0 three times), a
+  // self loop given once (2) and twice (3), node 5 with no edge at all
+  {
+    const int n = 6;
+    const std::vector<int64_t> s = {4, 1, 3, 2, 1, 3, 2, 1, 3, 4, 0}, t = {0, 0, 3, 0, 0, 0, 2, 0, 3, 0, 1};
+    std::vector<int64_t> e2(s);
+    e2.insert(e2.end(), t.begin(), t.end());
+    std::vector<int32_t> c2((size_t)n * W, -1);
+    std::vector<float> v2((size_t)n * W, -1.f);
+    CHECK(smaml_graph_ell(e2.data(), (int64_t)s.size(), n, c2.data(), v2.data()) == 0);
+    const int want0[W] = {4, 1, 2, 1, 3, 1, 4, 0};  // in input order, then the self loop in the eighth slot
+    for (int j = 0; j < W; ++j) CHECK(c2[j] == want0[j] && v2[j] > 0.f);
+    CHECK(std::fabs(v2[7] - 1.f / 8.f) < 1e-6f);                      // deg(0) = 7 + 1
+    CHECK(std::fabs(v2[1] - 1.f / std::sqrt(8.f * 2.f)) < 1e-6f);      // 1 -> 0: deg(1) = 1 + 1
+    for (int i : {2, 3, 5}) {  // input self loops replaced by one; an isolated node keeps it alone
+      CHECK(c2[(size_t)i * W] == i && v2[(size_t)i * W] == 1.f);
+      for (int j = 1; j < W; ++j) CHECK(c2[(size_t)i * W + j] == i && v2[(size_t)i * W + j] == 0.f);
+    }
+    std::vector<int64_t> e3(s);  // one more edge into node 0: in-degree 8
+    e3.push_back(3);
+    e3.insert(e3.end(), t.begin(), t.end());
+    e3.push_back(0);
+    CHECK(smaml_graph_ell(e3.data(), (int64_t)s.size() + 1, n, c2.data(), v2.data()) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "in-degree") != nullptr);
+    const std::vector<int64_t> negt = {0, 1, 1, -1};  // a negative target
+    CHECK(smaml_graph_ell(negt.data(), 2, n, c2.data(), v2.data()) == SMAML_EINVAL);
+    const std::vector<int64_t> loop7 = {7, 1, 7, 2};  // a self loop outside the graph
+    CHECK(smaml_graph_ell(loop7.data(), 2, n, c2.data(), v2.data()) == SMAML_EINVAL);
+  }
   CHECK(smaml_graph_ell(nullptr, 2, N, cols.data(), vals.data()) == SMAML_EINVAL);
   CHECK(smaml_graph_ell(ei.data(), E, 0, cols.data(), vals.data()) == SMAML_EINVAL);
 

@@ -1859,6 +1859,16 @@ int smaml_set_task_ids(smaml_ctx* c, const int32_t* ids_host, int32_t n) {
   return SMAML_OK;
 }
 
+// The graph entry points gather rows 0 .. num_nodes - 1 of x into the t = 0 block: an x with fewer rows than the
+// graph has nodes would be read past its end (PyG raises an IndexError there).
+static int check_gcn_rows(const smaml_ctx* c, int32_t rows, const char* who) {
+  if (rows < c->d.N)
+    return fail(SMAML_EINVAL, std::string(who) + ": rows (" + std::to_string(rows) + ") must be at least num_nodes (" +
+                                  std::to_string(c->d.N) + ") unless SMAML_GCN_PLAIN: the t = 0 block gathers rows 0 .. "
+                                  "num_nodes - 1 of x");
+  return SMAML_OK;
+}
+
 int smaml_gcn_conv(smaml_ctx* c, void* stream, const float* x, int32_t rows, int32_t cin, const float* weight,
                    const float* bias, int32_t cout, float* out) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
@@ -1867,10 +1877,11 @@ int smaml_gcn_conv(smaml_ctx* c, void* stream, const float* x, int32_t rows, int
     return fail(SMAML_EINVAL, "bad gcn_conv arguments");
   if (cin % 4) return fail(SMAML_EINVAL, "cin must be a multiple of 4");
   if (!aligned16(x) || !aligned16(weight)) return fail(SMAML_EINVAL, "x / weight must be 16-byte aligned");
+  TRY(check_gcn_rows(c, rows, "smaml_gcn_conv"));
   TRY(ensure_device(c));
   hipStream_t s = (hipStream_t)stream;
   launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, false, weight, bias, cin, cout,
-                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, std::min(rows, c->d.N));
+                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, c->d.N);
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1884,11 +1895,12 @@ int smaml_gcn_conv_ex(smaml_ctx* c, void* stream, const float* x, int32_t rows, 
     return fail(SMAML_EINVAL, "bad gcn_conv_ex arguments");
   if (cin % 4) return fail(SMAML_EINVAL, "cin must be a multiple of 4");
   if (!aligned16(x) || !aligned16(weight)) return fail(SMAML_EINVAL, "x / weight must be 16-byte aligned");
+  if (!plain) TRY(check_gcn_rows(c, rows, "smaml_gcn_conv_ex"));
   TRY(ensure_device(c));
   TRY(check_device_error(c));
   hipStream_t s = (hipStream_t)stream;
   launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, relu, weight, bias, cin, cout,
-                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, plain ? 0 : std::min(rows, c->d.N));
+                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, plain ? 0 : c->d.N);
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1903,11 +1915,12 @@ int smaml_gcn_conv_backward(smaml_ctx* c, void* stream, const float* x, int32_t 
   if (cin % 4 || cout % 4) return fail(SMAML_EINVAL, "cin and cout must be multiples of 4");
   if (!aligned16(x) || !aligned16(weight) || !aligned16(dz) || (dx && !aligned16(dx)))
     return fail(SMAML_EINVAL, "x / weight / dz / dx must be 16-byte aligned");
+  if (!plain) TRY(check_gcn_rows(c, rows, "smaml_gcn_conv_backward"));
   TRY(ensure_device(c));
   TRY(check_device_error(c));
   TRY(reserve(c, 1, 1));  // the split-K partial slabs of the weight gradient
   hipStream_t s = (hipStream_t)stream;
-  const int ng = plain ? 0 : std::min(rows, c->d.N);
+  const int ng = plain ? 0 : c->d.N;
   TRY(gcn_conv_bwd(c, s, x, rows, rows, cin, weight, cout, dz, ng, dx, dwb, 0, (int64_t)cout * cin));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;

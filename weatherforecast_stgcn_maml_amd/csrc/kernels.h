@@ -6,7 +6,7 @@
 
 namespace smaml {
 
-constexpr int ELLW = 8;        // ELL width of the normalised t=0 adjacency (max in-degree 6 + self)
+constexpr int ELLW = 8;        // ELL width of the normalised t=0 adjacency (max in-degree 7 + self)
 constexpr int MAX_LAYERS = 8;
 
 // Every host-built plan / launch-argument struct below gives each member a default initialiser, so a

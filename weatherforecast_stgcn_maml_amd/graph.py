@@ -36,10 +36,11 @@ def gcn_ell(edge_index: np.ndarray, num_nodes: int, width: int = ELL_WIDTH):
     self); any present are replaced, as PyG's ``add_remaining_self_loops`` does."""
     ei = np.asarray(edge_index, dtype=np.int64)
     src, dst = ei[0], ei[1]
+    # both rows, self loops included, before anything is indexed (numpy would wrap a negative target)
+    if ei.size and (ei.max() >= num_nodes or ei.min() < 0):
+        raise ValueError("edge_index references nodes outside [0, num_nodes)")
     keep = src != dst
     src, dst = src[keep], dst[keep]
-    if src.size and (src.max() >= num_nodes or dst.max() >= num_nodes or src.min() < 0):
-        raise ValueError("edge_index references nodes outside [0, num_nodes)")
     deg = np.ones(num_nodes, dtype=np.float64)
     np.add.at(deg, dst, 1.0)
     dinv = np.float32(1.0) / np.sqrt(deg.astype(np.float32))

@@ -89,7 +89,9 @@ class _Linear(nn.Module):
 class GCNConv(nn.Module):
     """PyG 2.x ``GCNConv(in, out)`` (normalize=True, add self loops, bias). forward
     runs ``smaml_gcn_conv``: rows < num_nodes of the graph aggregate over in-edges
-    (symmetric normalisation), all other rows see only their self loop (F3)."""
+    (symmetric normalisation), all other rows see only their self loop (F3). The graph has
+    ``edge_index.max() + 1`` nodes; an ``x`` with fewer rows raises ``SmamlError`` (``SMAML_EINVAL``,
+    "rows must be at least num_nodes") where PyG raises an ``IndexError``."""
 
     def __init__(self, in_channels, out_channels, **kwargs):
         super().__init__()
