@@ -46,7 +46,7 @@ typedef struct smaml_ctx smaml_ctx;
  * lstm_num_layers <= 8, forecast_horizon * output_channels <= 128, output_channels <= input_channels.
  * Every entry point that launches the LSTM or the head (smaml_forward, smaml_backward, smaml_backward_base, smaml_lstm_forward,
  * smaml_lstm_backward, smaml_head_loss, smaml_meta_step, smaml_inner_loop, smaml_adapt_prepare[_multi],
- * smaml_adapt_steps[_multi, _full], smaml_forecast, smaml_forecast_ensemble, smaml_forecast_rollout) requires in addition
+ * smaml_adapt_steps[_multi, _full], smaml_forecast, smaml_forecast_ensemble, smaml_forecast_rollout[_ensemble]) requires in addition
  *   hidden_channels % 16 == 0                        (the layer-0 K segment of the gate-GEMM tile loaders)
  *   (forecast_horizon * output_channels) % 4 == 0    (16-byte reads of prediction rows)
  * and returns SMAML_EINVAL naming the dimension otherwise, before it allocates or launches anything. */
@@ -195,7 +195,7 @@ int smaml_forecast(smaml_ctx* ctx, void* stream, const float* theta, int32_t tas
                    int32_t nwin, int32_t batch, const float* scale_host, float* pred, double* skill);
 
 /* Bytes of device memory the forecast's own buffers hold (not part of smaml_workspace_bytes; those of
- * smaml_forecast_ensemble included). */
+ * smaml_forecast_ensemble, smaml_forecast_rollout and smaml_forecast_rollout_ensemble included). */
 int64_t smaml_forecast_bytes(const smaml_ctx* ctx);
 
 /* Autoregressive rollout: the forecast fed back in, to reach lead times past the model's Hf steps. New; the
@@ -286,6 +286,65 @@ int smaml_forecast_ensemble(smaml_ctx* ctx, void* stream, const float* theta, in
                             const int32_t* windows_host, int32_t nwin, int32_t batch, int32_t members, float p_gcn,
                             float p_lstm, uint32_t seed, const float* scale_host, float* mean, float* spread,
                             float* member_pred, double* scores);
+
+/* Ensemble rollout: `members` (E, 1..64) MC-dropout members, each fed its OWN forecast back in for `cycles`
+ * (R, 1..1024) cycles -- how the ensemble spread grows with lead time. Notation as smaml_forecast_rollout:
+ * s = Hf + 1, origin i = origins_host[i] in task `task`'s stream S.
+ *   Member e of origin i keeps a private sequence X(e,i), X(e,i)[rho] = S[o_i + rho] for rho < T. Cycle j: the
+ *   window is X(e,i)[j s : j s + T]; the output P(e,i) is what HybridSTGCN_LSTM.train()'s forward under no_grad
+ *   computes on that window with this library's counter-based masks.
+ *   Masks: the sites drop_site(seed, kind, step = 64 j + e, layer) with task id 0; the element indices are those
+ *   of the training forward of ONE batch holding the whole origin list (B := norig, sample b := i, M := norig*N,
+ *   row m := i*N + n): the three index lines of smaml_forecast_ensemble, t the step inside the window. Member
+ *   e's oracle for cycle j is refcpu.stgcn_features(x_i, ei, Pg, drop, i, norig) per origin, then
+ *   refcpu.batched_forward(P, feats, dims, drop), drop = refcpu.Dropout(seed, p_gcn, p_lstm, 0, 64*j + e). A member
+ *   depends on none of: `batch`, how origins are cut into passes, the member grouping, E, R. Cycle 0 is by
+ *   definition smaml_forecast_ensemble's member e on the window list `origins`. The probabilities and the seed are
+ *   this call's arguments: smaml_set_dropout / smaml_set_task_ids are neither read nor written.
+ *   Append: smaml_forecast_rollout's rule, per member from its own P(e,i): the gap row by midpoint (gap = 1) or
+ *   persistence (gap = 0) in f32, then the Hf rows of P; channels c >= C from the stream.
+ *   Checked before anything is allocated or launched, SMAML_EINVAL with a message; the first line before a
+ *   context or device is needed: member_traj, mean, spread and scores all NULL; norig or batch <= 0; members
+ *   outside 1..64; cycles outside 1..1024 (the mask site packs step << 8 below kind << 24, so the step
+ *   64 j + e has 16 bits: 64 * 1023 + 63 = 65535 is the last that fits); a probability outside [0, 1); gap
+ *   outside {0, 1}. Then, naming the origin: o >= 0, o + T + (R - 1) s <= t_total, with `scores`
+ *   o + T + R s <= t_total.
+ *   Outputs, all optional, on the device, normalised:
+ *   member_traj [E][norig][R][s][N][C]: row 0 of a cycle is the gap row, rows 1..Hf the memory image of P.
+ *   mean, spread [norig][R][s][N][C]: the member sum in member order divided by E; the unbiased standard
+ *   deviation about that mean (two-pass, accumulated in double, rounded once), 0 at E = 1.
+ *   scores (doubles) [4][R s][C], overwritten: per absolute lead k = j s + r and variable, sums over origins and
+ *   nodes of every trajectory row (gap rows included) against y = S[o + T + k], s_c = scale_host[c] (NULL = 1):
+ *     [0] sum (s_c (mu - y))^2     [1] sum s_c^2 sigma^2
+ *     [2] sum s_c CRPS, CRPS = (1/E) sum_i |x_i - y| - (1/E^2) sum_{i<j} |x_i - x_j| (pairs in lexicographic order)
+ *     [3] sum (s_c (y_last - y))^2, y_last = S[o + T - 1]
+ *   Fixed order: f32 per block, double across blocks and passes, no atomics. Bitwise repeatable.
+ * Origins run in passes of at most `batch`; within a pass the members run G at a time over grid z, every
+ * (member, origin) pair of a group in lockstep through the R cycles. G = option ens_group (0 = all), default the
+ * largest group whose rings, slot tables, sequences and features fit option roll_ens_budget_mb (floor 1). Any
+ * grouping is bitwise equal. With p_gcn == 0 the eval-form GCN is position-independent: the observed rows
+ * (rho < T) are the same in every member, so their features and layer-0 projection are computed once per pass
+ * into a table all members read, and only the rows a member appended go through the GCN and projection per
+ * member (option roll_reuse; 0 recomputes every row per member and cycle: bitwise equal). In cycle 0 all members
+ * read the same window: its t = 0 graph block is computed once, and with two or more LSTM layers layer 0 runs
+ * once (option ens_share); from cycle 1 on both are per member. With p_gcn > 0 the kind-1 masks depend on cycle
+ * and position: every member recomputes all T rows each cycle on the per-layer kernels (correct, not tuned).
+ * State isolation as the other forecast calls: buffers of its own (grow only, in smaml_forecast_bytes), the
+ * workspace, the adaptation cache and the meta-step state untouched, a pending smaml_forward / smaml_backward
+ * pair stays valid, no stream synchronisation. */
+int smaml_forecast_rollout_ensemble(smaml_ctx* ctx, void* stream, const float* theta, int32_t task,
+                                    const int32_t* origins_host, int32_t norig, int32_t batch, int32_t cycles,
+                                    int32_t gap, int32_t members, float p_gcn, float p_lstm, uint32_t seed,
+                                    const float* scale_host, float* member_traj, float* mean, float* spread,
+                                    double* scores);
+
+/* Host-side counters of the last smaml_forecast_rollout_ensemble call that passed its checks, summed over its
+ * passes and member groups; a "row" is one time step of one origin (N node rows): [0] cycles run (one per group
+ * and cycle), [1] member-rows through the position-independent GCN (with roll_reuse and p_gcn == 0:
+ * E norig (R - 1) min(s, T - 1)), [2] shared rows through it (observed rows, once per pass: norig (T - 1)),
+ * [3] rows through the t = 0 graph path, [4] rows of layer-0 projection computed ([1] + [2] + [3]; none at p_gcn > 0), [5] append launches,
+ * [6] member groups run. Writes min(cap, count) entries; *count = 7. Measurement and tests. */
+int smaml_rollout_ensemble_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
 
 /* One meta-step over all registered tasks (meta_update_v4, train_hybrid_maml_v5.py:144-184,
  * wrapping inner_loop_v4, :110-141):
@@ -575,6 +634,15 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  origins x 15 cycles, 44.1 ms (44.0-44.4) against 54.0 ms (53.9-54.1) with 0,
  *                                  outside both spreads (profiles/rollout_bench.log; a Python loop of
  *                                  smaml_forecast calls per cycle: 53.9 ms);
+ *   "roll_ens_budget_mb":          smaml_forecast_rollout_ensemble, with ens_group at -1, runs as many members at
+ *                                  a time as fit this many MiB of rings, slot tables, sequences and features
+ *                                  (at least one; 1 .. 2^20; bitwise equal). Default 32768: at config-2 shapes,
+ *                                  32 origins x 15 cycles x 16 members (1.39 GB per member) all 16 at once
+ *                                  took 644.7 ms (644.0-645.1) against 651.9 (8 at a time), 664.0 (4) and
+ *                                  722.1 ms (721.1-722.4; one at a time, which is what the ensemble's 2 GiB
+ *                                  leaves here), each outside the others' spreads
+ *                                  (profiles/ensemble_rollout_bench.log). ens_share and roll_reuse apply to this
+ *                                  call too: 650.4 ms with ens_share 0, 828.9 ms with roll_reuse 0;
  *   "adapt_group":                 smaml_adapt_steps_multi runs its regions this many at a time, each group
  *                                  as one set of launches per step (0: all at once; at most 64; -1, the
  *                                  default: the measured plan -- 3 to 5 regions in sets of 2, where a set

@@ -29,8 +29,20 @@ origins, R cycles of Hf + 1 steps, one pass, the trajectory only, in three arms:
                     channels) into a new stream for set_tasks
 and prints smaml_rollout_stats of the reuse arms and how far the loop's trajectory is from the library's.
 
+With --rollout R --members E the tool times the ensemble rollout (smaml_forecast_rollout_ensemble) instead: E
+members over --origins (32) origins, R cycles, one pass, p_lstm = 0.2, the statistics only (scores), against the
+arm `deterministic`: smaml_forecast_rollout of the same origins (skill sums only) in the same run, whose median
+times E is the yardstick (E separate deterministic rollouts). Arms:
+  ens                 the library call as shipped (p_gcn = 0, every option at its default)
+  ens_group_1/4/8/all option ens_group forced (all = 0; a budget large enough for E members plans the same groups)
+  ens_budget_2048     option roll_ens_budget_mb at the 2 GiB of smaml_forecast_ensemble's plan (default grouping)
+  ens_share_0         ens_share 0 at ens_group all: LSTM layer 0 of cycle 0 per member
+  ens_reuse_0         roll_reuse 0 at ens_group all: every row of every window per member and cycle
+  ens_pgcn0.2         p_gcn = 0.2 (per-member GCN on the per-layer kernels), default grouping
+and prints smaml_rollout_ensemble_stats and smaml_forecast_bytes of every arm.
+
 Usage: python tools/bench_forecast.py [--reps 5] [--warmup 1] [--windows 1200] [--members E [--batch 32] [--group G]]
-       python tools/bench_forecast.py --rollout 15 [--origins 32]
+       python tools/bench_forecast.py --rollout 15 [--origins 32] [--members 16]
 """
 from __future__ import annotations
 
@@ -85,6 +97,8 @@ def main():
         ctx.set_tasks([stream_t])
         return ctx
 
+    if a.rollout > 0 and a.members > 0:
+        return rollout_ensemble_main(a, d, context, theta, st, torch)
     if a.rollout > 0:
         return rollout_main(a, d, context, theta, stream_t, st, torch)
     if a.members > 0:
@@ -328,6 +342,101 @@ def rollout_main(a, d, context, theta, stream_t, st, torch):
         "value": B * R / (res["rollout"]["median_ms"] * 1e-3), "unit": "origin-cycles/s", "higher_is_better": True,
         "origins": B, "cycles": R, "reps": a.reps, "warmup": a.warmup, "arms": res, "rollout_stats": stats,
         "python_loop_rel_l2": drift,
+        "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
+
+
+def rollout_ensemble_main(a, d, context, theta, st, torch):
+    R, B, E = a.rollout, a.origins, a.members
+    s, N, C = d.forecast_horizon + 1, d.num_nodes, d.output_channels
+    dev = theta.device
+    origins = list(range(B))
+    out, stats = {}, {}
+    det_ctx = context()
+    skill = torch.zeros(3, R * s, C, device=dev, dtype=torch.float64)
+
+    def det():
+        det_ctx.forecast_rollout(st, theta, origins, B, R, 1, skill=skill)
+        torch.cuda.synchronize()
+        out["deterministic"] = skill.cpu().numpy()
+
+    def ens_arm(key, p_gcn=0.0, **opts):
+        ctx = context()
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        scores = torch.zeros(4, R * s, C, device=dev, dtype=torch.float64)
+
+        def run():
+            ctx.forecast_rollout_ensemble(st, theta, origins, B, R, E, p_gcn, 0.2, 12345, scores=scores)
+            torch.cuda.synchronize()
+            out[key] = scores.cpu().numpy()
+            stats[key] = ctx.rollout_ensemble_stats()
+        return run, ctx
+
+    arms = {"deterministic": (det, det_ctx), "ens": ens_arm("ens")}
+    for g, name in ((1, "1"), (4, "4"), (8, "8"), (0, "all")):
+        arms[f"ens_group_{name}"] = ens_arm(f"ens_group_{name}", ens_group=g)
+    arms["ens_budget_2048"] = ens_arm("ens_budget_2048", roll_ens_budget_mb=2048)
+    arms["ens_share_0"] = ens_arm("ens_share_0", ens_group=0, ens_share=0)
+    arms["ens_reuse_0"] = ens_arm("ens_reuse_0", ens_group=0, roll_reuse=0)
+    arms["ens_pgcn0.2"] = ens_arm("ens_pgcn0.2", p_gcn=0.2)
+    times = {k: [] for k in arms}
+    for _ in range(a.warmup):
+        for fn, _ in arms.values():
+            fn()
+    for _ in range(a.reps):
+        for k, (fn, _) in arms.items():  # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    cats = {}
+    for k, (fn, ctx) in arms.items():
+        ctx.timing(True)
+        ctx.timing_collect()
+        fn()
+        cats[k] = {c: v for c, v in ctx.timing_collect().items() if v["launches"]}
+        ctx.timing(False)
+    for k, v in out.items():
+        assert np.isfinite(v).all(), k
+    for k in out:  # grouping, sharing and reuse change no bit
+        if k not in ("deterministic", "ens", "ens_pgcn0.2"):
+            assert np.array_equal(out[k], out["ens"]), k
+    # the persistence sums are the deterministic rollout's (same targets, same blocks)
+    assert np.allclose(out["ens"][3], out["deterministic"][2], rtol=1e-6)
+    res = {}
+    for k, ts in times.items():
+        ms = np.asarray(ts) * 1e3
+        res[k] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+    yard = E * res["deterministic"]["median_ms"]
+    print(f"{E} members x {B} origins x {R} cycles of {s} steps (N = {N}, T = {d.window_size}), one pass, scores only, "
+          f"{a.reps} reps after {a.warmup} warm-up")
+    for k, r in res.items():
+        line = f"{k:16s} median {r['median_ms']:9.2f} ms  (min {r['min_ms']:.2f} - max {r['max_ms']:.2f})"
+        if k != "deterministic":
+            r["vs_E_x_deterministic"] = r["median_ms"] / yard
+            line += f"  = {r['vs_E_x_deterministic']:.3f} x ({E} x deterministic = {yard:.1f} ms)"
+        print(line)
+
+    def apart(x, y):
+        return x["max_ms"] < y["min_ms"] or y["max_ms"] < x["min_ms"]
+
+    al = res["ens_group_all"]
+    for k in ("ens_group_1", "ens_group_4", "ens_group_8", "ens_budget_2048", "ens_share_0", "ens_reuse_0"):
+        print(f"ens_group_all / {k} = {al['median_ms'] / res[k]['median_ms']:.3f} "
+              f"(ranges {'do not overlap' if apart(al, res[k]) else 'overlap'})")
+    for k, v in stats.items():
+        print(f"smaml_rollout_ensemble_stats {k}: {v}")
+    fbytes = {k: ctx.forecast_bytes() for k, (_, ctx) in arms.items()}
+    for k, b in fbytes.items():
+        print(f"smaml_forecast_bytes {k}: {b} ({b / 2**20:.0f} MiB)")
+    for k, c in cats.items():
+        print(f"{k} kernel ms by category: " + ", ".join(f"{n} {v['ms']:.1f} ({v['launches']})" for n, v in c.items()))
+    print(json.dumps({
+        "metric": f"{E}-member {R}-cycle ensemble rollout + scores, member-origin-cycles/sec (N=441, T=24, config-2 "
+                  f"dims, {B} origins, p_gcn=0)",
+        "value": E * B * R / (res["ens"]["median_ms"] * 1e-3), "unit": "member-origin-cycles/s",
+        "higher_is_better": True, "members": E, "origins": B, "cycles": R, "reps": a.reps, "warmup": a.warmup,
+        "arms": res, "stats": stats, "forecast_bytes": fbytes,
         "kernel_ms": {k: {n: v["ms"] for n, v in c.items()} for k, c in cats.items()}}))
 
 

@@ -27,6 +27,7 @@ EXPORTS = (
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
     "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
     "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
+    "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -135,6 +136,14 @@ _SIGS["smaml_rollout_stats"] = ([P, PI64, I32, PI32], I32)
 # smaml_rollout_stats order (host counters of the last smaml_forecast_rollout call; a row = one time step of one origin)
 ROLLOUT_STATS = ("cycles", "gcn_rows", "graph_rows", "xg_rows", "append_launches")
 ROLLOUT_GAPS = {"persistence": 0, "midpoint": 1}  # smaml_forecast_rollout's gap argument
+_SIGS["smaml_forecast_rollout_ensemble"] = ([P, P, P, I32, PI32, I32, I32, I32, I32, I32, F32, F32, ctypes.c_uint32, PF32,
+                                             P, P, P, P], I32)
+_SIGS["smaml_rollout_ensemble_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_rollout_ensemble_stats order (host counters of the last smaml_forecast_rollout_ensemble call; a row = one
+# time step of one origin; member_rows / shared_rows went through the position-independent GCN)
+ROLLOUT_ENSEMBLE_STATS = ("cycles", "member_rows", "shared_rows", "graph_rows", "xg_rows", "append_launches",
+                          "member_groups")
+ROLLOUT_ENSEMBLE_MAX_CYCLES = 1024  # the mask site's step 64 j + e has 16 bits
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
 
@@ -432,6 +441,33 @@ class Context:
         check(self._L.smaml_rollout_stats(self._h, buf, n, ctypes.byref(cnt)))
         assert cnt.value == n, (cnt.value, n)
         return {name: int(buf[i]) for i, name in enumerate(ROLLOUT_STATS)}
+
+    def forecast_rollout_ensemble(self, stream, theta, origins, batch, cycles, members, p_gcn, p_lstm, seed, gap=1,
+                                  task=0, scale=None, member_traj=None, mean=None, spread=None, scores=None):
+        """Ensemble rollout (smaml_forecast_rollout_ensemble): ``members`` MC-dropout members, each fed its own
+        forecast back in for ``cycles`` cycles; member ``e`` of cycle ``j`` under the masks of ``(seed, step 64 j +
+        e)``. Device tensors, each optional: ``member_traj`` [members, norig, cycles, Hf + 1, N, C], ``mean`` /
+        ``spread`` [norig, cycles, Hf + 1, N, C] float32, ``scores`` [4, cycles * (Hf + 1), C] float64
+        (``forecast.ENSEMBLE_SUMS``; ``scale`` = their per-variable factors, host, [C]); ``gap`` as
+        ``forecast_rollout``."""
+        o = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+        if sc is not None and sc.size != self.dims.output_channels:
+            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
+        check(self._L.smaml_forecast_rollout_ensemble(
+            self._h, stream, ptr(theta), int(task), o.ctypes.data_as(PI32), o.size, int(batch), int(cycles), int(gap),
+            int(members), float(p_gcn), float(p_lstm), int(seed) & 0xFFFFFFFF,
+            sc.ctypes.data_as(PF32) if sc is not None else None, opt(member_traj), opt(mean), opt(spread), opt(scores)))
+
+    def rollout_ensemble_stats(self):
+        """{counter: count} of the last forecast_rollout_ensemble call (host counters, no sync)."""
+        n = len(ROLLOUT_ENSEMBLE_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_rollout_ensemble_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(ROLLOUT_ENSEMBLE_STATS)}
 
     def forecast_bytes(self):
         return int(self._L.smaml_forecast_bytes(self._h))

@@ -382,6 +382,18 @@ struct smaml_ctx {
   HipBuf ro_blk;            // [B][s][N][C]
   int roll_reuse = 1;       // smaml_set_option("roll_reuse"): only the appended rows get features and projection
   int64_t ro_stats[5] = {}; // smaml_rollout_stats: counters of the last smaml_forecast_rollout call
+  // smaml_forecast_rollout_ensemble shares fc_F, fc_gcnA / B, fc_part, fc_scale, ens_ring and ens_pred, and adds
+  // the members' private sequences and slot tables, the observed rows' projection that all members read, the
+  // t = 0 rows' features and (no member_traj) the pass's trajectories
+  HipBuf re_seq;            // [G][B][T + (R - 1) s][N][Cin]
+  HipBuf re_xg;             // [S][G][M][4H]: slot rho % S of appended row rho, per member; then [G][M][4H], t = 0
+  HipBuf re_obs;            // [T][M][4H]: observed row rho (shared by the members); then [M][4H], cycle 0's t = 0
+  HipBuf re_F0;             // [G][M][Hc]
+  HipBuf re_traj;           // [E][B][R][s][N][C]
+  bool rens_lds_set = false;      // k_rens_stats's dynamic-LDS limit raised (rens_stats_prepare)
+  int64_t roll_ens_budget_mb = 32768; // smaml_set_option("roll_ens_budget_mb"): MiB a member group may take (measured:
+                                      // 16 members at once 10 % faster than one at a time at config-2 shapes)
+  int64_t re_stats[7] = {}; // smaml_rollout_ensemble_stats
   // side streams of the row-chunked BPTT (knob bptt_streams) and their fork / join events
   hipStream_t cs[4] = {};
   hipEvent_t fork_ev = nullptr, join_ev[4] = {};
@@ -2046,7 +2058,7 @@ int64_t smaml_forecast_bytes(const smaml_ctx* c) {
   if (!c) return 0;
   return c->fc_ring.cap + c->fc_F.cap + c->fc_gcnA.cap + c->fc_gcnB.cap + c->fc_xg.cap + c->fc_pred.cap +
          c->fc_part.cap + c->fc_scale.cap + c->ens_ring.cap + c->ens_pred.cap + c->ro_seq.cap + c->ro_xg.cap +
-         c->ro_F0.cap + c->ro_blk.cap;
+         c->ro_F0.cap + c->ro_blk.cap + c->re_seq.cap + c->re_xg.cap + c->re_obs.cap + c->re_F0.cap + c->re_traj.cap;
 }
 
 // ---- smaml_forecast_rollout: the forecast fed back in, cycle by cycle ------------------------------------
@@ -2288,6 +2300,394 @@ int smaml_rollout_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_
   if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad rollout_stats arguments");
   for (int i = 0; i < 5 && i < cap; ++i) counts[i] = c->ro_stats[i];
   if (count) *count = 5;
+  return SMAML_OK;
+}
+
+// ---- smaml_forecast_rollout_ensemble: MC-dropout members through the fed-back forecast -------------------
+namespace {
+constexpr int RENS_MAX_CYCLES = 1024;  // drop_site gives `step` 16 bits (step << 8 below kind << 24): 64 j + e < 2^16
+
+struct RensPlan {
+  int R = 0, gap = 0, E = 0, G = 0, Bmax = 0, Btail = 0, S = 0;
+  float p_gcn = 0.f, p_lstm = 0.f;
+  uint32_t seed = 0;
+  int64_t norig = 0;
+  bool reuse = true, fused = false;
+  // the uploaded table: src[norig] (origin rows), obs[norig] (the same one step on), then for the pass size
+  // Bmax and, behind it, for the last pass's Btail: per cycle win[G * B], run[G * B], entry z * B + b
+  int64_t tab_src = 0, tab_obs = 0, tab_cyc[2] = {0, 0};
+};
+
+// floats of one member of a pass of M rows: rings, slot table with its t = 0 block, sequences, features
+int64_t rens_member_bytes(const Dims& d, int B, int R, bool per_member_F) {
+  const int64_t M = (int64_t)B * d.N, sl = d.Hf + 1;
+  const int64_t f = 2 * infer_ring_floats(d, 1, (int)M) + (d.T + 1) * M * 4 * d.H +
+                    (int64_t)B * (d.T + (int64_t)(R - 1) * sl) * d.N * d.Cin0 +
+                    (per_member_F ? (int64_t)d.T : std::max(d.T - 1, 1)) * M * d.Hc + M * d.Hc;
+  return f * 4;
+}
+
+// One pass of B origins (first of them `done`): the members G at a time over grid z, every (member, origin)
+// pair of a group in lockstep through the R cycles; then the pass's statistics from all E trajectories.
+int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p, int64_t done, int B,
+              const float* scale_dev, float* member_traj, float* mean, float* spread, double* scores) {
+  const Dims& d = c->d;
+  const int M = B * d.N, sl = d.Hf + 1, S = p.S, E = p.E;
+  const bool shared = p.p_gcn == 0.f, obs = shared && p.reuse;
+  const int64_t blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H, fslab = (int64_t)d.T * M * d.Hc;
+  Work w{};
+  w.Z = 1;
+  w.B = B;
+  w.M = M;
+  w.F = c->fc_F.as<float>();
+  w.gcnA = c->fc_gcnA.as<float>();
+  w.gcnB = c->fc_gcnB.as<float>();
+  w.vcount = c->vcount;
+  w.kn = c->kn;
+  c->w = w;
+  TRY(prep_gate_images(c, s, theta, 0));
+  Work& cw = c->w;
+  const bool img = cw.gimg.th && cw.gimg_src == theta;
+  const char* gimg = img ? cw.gimg.th : nullptr;
+  const int64_t gimg_off = cw.gimg.off[0][0];
+  const int32_t* ell_c = c->ell_c.as<int32_t>();
+  const float* ell_v = c->ell_v.as<float>();
+  const int cin0 = c->po.lay[0].cin;
+  GcnWOff wo;
+  for (int k = 0; k < 4; ++k) {
+    wo.w[k] = c->go.w[k];
+    wo.b[k] = c->go.b[k];
+  }
+  if (shared && p.fused) TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, c->gcn_wimg.as<char>()));
+  float* bufs[2] = {cw.gcnA, cw.gcnB};
+  float* Frun = c->fc_F.as<float>();
+  // the per-layer chain over `ns` samples of rps rows each (the first ell_rows of them aggregate over the
+  // graph), time-major into dst over all ns samples; in chunks of samples whose buffers stay below 2^30 bytes
+  // (the layer kernel's loaders index in 32 bits)
+  auto gcn_chain = [&](const float* const* tab, int ns, int rps, int ell_rows, float* dst) {
+    const int cs = (int)std::max<int64_t>(1, (1ll << 28) / ((int64_t)rps * d.Hc));
+    for (int s0 = 0; s0 < ns; s0 += cs) {
+      const int n = std::min(cs, ns - s0);
+      const float* from = nullptr;
+      for (int k = 0; k < 4; ++k) {
+        const bool last = k == 3;
+        float* to = last ? dst + (int64_t)s0 * d.N * d.Hc : bufs[k & 1];
+        TIMED(c, s, C_GCN, 2.0 * n * rps * c->go.cin[k] * d.Hc,
+              launch_gcn_layer(s, d, k, n, ns, k == 0 ? tab + s0 : nullptr, from, to, last, true, c->gcn + c->go.w[k],
+                               c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, ell_rows, nullptr,
+                               d.T * d.N));
+        from = to;
+      }
+    }
+  };
+  // layer 0's projection of plain rows, in launches whose output stays below 2^32 bytes (k_xg_dedup's stores
+  // index in 32 bits)
+  auto xg_rows = [&](const float* F, int64_t rows, float* out) {
+    const int64_t cr = ((1ll << 30) / (4 * d.H) - 1) / 256 * 256;
+    for (int64_t r = 0; r < rows; r += cr) {
+      const int64_t n = std::min(cr, rows - r);
+      TIMED(c, s, C_XG, 2.0 * n * 4 * d.H * cin0,
+            launch_xg_rows(s, d, cw, F + r * d.Hc, n, theta, c->po, gimg, gimg_off, out + r * 4 * d.H));
+    }
+    c->re_stats[4] += rows / d.N;
+  };
+  const float* const* src = nullptr;
+  const float* const* otab = nullptr;
+  TRY(xtab_at(c, p.tab_src + done, &src));
+  TRY(xtab_at(c, p.tab_obs + done, &otab));
+  float* xobs = c->re_obs.as<float>();
+  float* xobs0 = xobs + (int64_t)d.T * slot;
+  float* F0 = c->re_F0.as<float>();
+  if (obs) {
+    // what every member reads unchanged: the observed rows 1 .. T - 1 (position-independent GCN, projection)
+    // and cycle 0's t = 0 block, once for the pass
+    const int nobs = d.T - 1;
+    if (nobs > 0) {
+      if (p.fused)
+        TIMED(c, s, C_GCN, 2.0 * B * nobs * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+              launch_gcn_mlp_run(s, d, B, nobs, otab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
+      else
+        gcn_chain(otab, B, nobs * d.N, 0, Frun);
+      xg_rows(Frun, (int64_t)nobs * M, xobs + slot);
+      c->re_stats[2] += (int64_t)B * nobs;
+    }
+    gcn_chain(src, B, d.N, d.N, F0);
+    xg_rows(F0, M, xobs0);
+    c->re_stats[3] += B;
+  }
+  RollArgs ra{};
+  ra.seq = c->re_seq.as<float>();
+  ra.seq_rows = d.T + (p.R - 1) * sl;
+  ra.seq_stride = (int64_t)ra.seq_rows * d.N * d.Cin0;
+  ra.src = src;
+  ra.B = B;
+  ra.N = d.N;
+  ra.Cin = d.Cin0;
+  ra.C = d.C;
+  ra.Hf = d.Hf;
+  ra.T = d.T;
+  const int which = B == p.Bmax ? 0 : 1;  // (the table set laid out for this pass size)
+  const int64_t tabGB = (int64_t)p.G * B;
+  float* traj = member_traj ? member_traj + done * p.R * blkf : c->re_traj.as<float>();
+  const int64_t tstride = (member_traj ? p.norig : (int64_t)B) * p.R * blkf;  // floats between two members
+  EnsDrop ed{};
+  ed.seed = p.seed;
+  ed.thr = (uint32_t)std::lround((double)p.p_lstm * 16777216.0);
+  ed.sc = 1.f / (1.f - p.p_lstm);
+  ed.row0 = done * d.N;
+  ed.Mtot = p.norig * d.N;
+  const uint32_t thr_gcn = (uint32_t)std::lround((double)p.p_gcn * 16777216.0);
+  float* P = c->ens_pred.as<float>();
+  for (int e0 = 0; e0 < E; e0 += p.G) {
+    const int g = std::min(p.G, E - e0);
+    const int64_t ring = infer_ring_floats(d, g, M);
+    float* ringH = c->ens_ring.as<float>();
+    float* ringC = ringH + ring;
+    float* xg = c->re_xg.as<float>();           // [S][g][M][4H]
+    float* xg0 = xg + (int64_t)S * g * slot;    // [g][M][4H]
+    TIMED(c, s, C_MISC, 0, launch_rollout_init(s, ra, g));
+    c->re_stats[6] += 1;
+    for (int j = 0; j < p.R; ++j) {
+      const float* const* wtab = nullptr;
+      const float* const* rtab = nullptr;
+      TRY(xtab_at(c, p.tab_cyc[which] + (int64_t)j * 2 * tabGB, &wtab));
+      TRY(xtab_at(c, p.tab_cyc[which] + ((int64_t)j * 2 + 1) * tabGB, &rtab));
+      const bool first_shared = obs && j == 0;  // every block of cycle 0 is in the shared table
+      if (!shared) {
+        // each member's GCN under its own kind-1 masks of step 64 j + e (smaml_forecast_ensemble's path): all T
+        // rows of its window, every cycle
+        const int rps = d.T * d.N;
+        for (int z = 0; z < g; ++z) {
+          const float* from = nullptr;
+          for (int k = 0; k < 4; ++k) {
+            const bool last = k == 3;
+            float* to = last ? Frun + (int64_t)z * fslab : bufs[k & 1];
+            TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
+                  launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab + (int64_t)z * B : nullptr, from, to, last, true,
+                                   c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N,
+                                   nullptr));
+            if (!last)
+              TIMED(c, s, C_GCN, 0,
+                    launch_ens_dropout(s, to, (int64_t)B * rps * d.Hc, 1, p.seed, 1, 64 * j + e0 + z, k, thr_gcn,
+                                       1.f / (1.f - p.p_gcn), (uint64_t)done * rps * d.Hc));
+            from = to;
+          }
+        }
+        c->re_stats[1] += (int64_t)g * B * (d.T - 1);
+        c->re_stats[3] += (int64_t)g * B;
+        cw.xgd = XgDedup{};
+      } else {
+        if (!first_shared) {
+          // the rows t >= 1 the members owe (with reuse: those they appended in the previous cycle), g B samples
+          // in one launch, time-major over the group, then into their slots (a run that wraps takes two)
+          const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
+          if (nrun > 0) {
+            if (p.fused)
+              TIMED(c, s, C_GCN, 2.0 * g * B * nrun * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+                    launch_gcn_mlp_run(s, d, g * B, nrun, rtab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
+            else
+              gcn_chain(rtab, g * B, nrun * d.N, 0, Frun);
+            for (int tau = 0; tau < nrun;) {
+              const int sl0 = (r0 + tau) % S, len = std::min(nrun - tau, S - sl0);
+              xg_rows(Frun + (int64_t)tau * g * M * d.Hc, (int64_t)len * g * M, xg + (int64_t)sl0 * g * slot);
+              tau += len;
+            }
+            c->re_stats[1] += (int64_t)g * B * nrun;
+          }
+          gcn_chain(wtab, g * B, d.N, d.N, F0);
+          xg_rows(F0, (int64_t)g * M, xg0);
+          c->re_stats[3] += (int64_t)g * B;
+        }
+        XgDedup xd{};
+        xd.xg = xg;
+        xd.xg0 = first_shared ? xobs0 : xg0;
+        xd.src = theta;
+        xd.N = d.N;
+        xd.ring_S = S;
+        cw.xgd = xd;
+        ed.xg0_z = first_shared ? 0 : slot;
+        ed.xg_obs = obs ? xobs : nullptr;
+        ed.obs_rows = obs ? d.T : 0;
+        ed.ring_row = j * sl;
+      }
+      ed.e0 = 64 * j + e0;
+      // cycle 0's windows are the same in every member: with nothing masked below layer 0's output, layer 0 once
+      ed.share0 = shared && j == 0 && c->ens_share && d.L > 1 ? 1 : 0;
+      for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+        FwdWave wv{};
+        double fl = 0.0;
+        fwd_wave(d, cw, c->po, diag, 0, false, wv);
+        for (int q = 0; q < wv.n; ++q) {
+          const double k1 = (wv.l[q] == 0 && shared ? 0 : wv.lo[q].cin) + (wv.t[q] > 0 ? d.H : 0);
+          fl += 2.0 * (wv.l[q] == 0 && ed.share0 ? 1 : g) * M * 4 * d.H * k1;
+        }
+        TIMED(c, s, C_FWD, fl,
+              launch_lstm_fwd_infer_drop(s, d, cw, diag, theta, c->po, ringH, ringC, g, shared ? 0 : fslab, ed));
+      }
+      float* hT = ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * g * M * d.H;
+      if (ed.thr)
+        TIMED(c, s, C_HEAD, 0,
+              launch_ens_dropout(s, hT, (int64_t)M * d.H, g, p.seed, 3, ed.e0, 0, ed.thr, ed.sc,
+                                 (uint64_t)ed.row0 * d.H));
+      Work hw = cw;
+      hw.Z = g;
+      TIMED(c, s, C_HEAD, 2.0 * g * M * d.HfC * d.H,
+            launch_head_pred(s, d, hw, hT, (int64_t)M * d.H, theta, 0, c->po, P));
+      TIMED(c, s, C_MISC, 0,
+            launch_rollout_append(s, ra, j, p.gap, j + 1 < p.R, P, traj + e0 * tstride + (int64_t)j * blkf,
+                                  (int64_t)p.R * blkf, g, tstride));
+      c->re_stats[5] += 1;
+      c->re_stats[0] += 1;
+    }
+  }
+  if (mean || spread || scores) {
+    if (E > 32 && !c->rens_lds_set) {
+      const hipError_t st = rens_stats_prepare();
+      if (st != hipSuccess)
+        return fail(SMAML_EHIP, std::string("smaml_forecast_rollout_ensemble: raising k_rens_stats's dynamic LDS limit "
+                                            "to 64 KB (more than 32 members) failed: ") + hipGetErrorString(st));
+      c->rens_lds_set = true;
+    }
+    const int64_t off = done * p.R * blkf;
+    TIMED(c, s, C_MISC, 0,
+          launch_rens_stats(s, d, B, E, p.R * sl, traj, tstride, src, scale_dev, mean ? mean + off : nullptr,
+                            spread ? spread + off : nullptr, c->fc_part.as<float>(), scores, done == 0));
+  }
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+}  // namespace
+
+int smaml_forecast_rollout_ensemble(smaml_ctx* c, void* stream, const float* theta, int32_t task,
+                                    const int32_t* origins_host, int32_t norig, int32_t batch, int32_t cycles,
+                                    int32_t gap, int32_t members, float p_gcn, float p_lstm, uint32_t seed,
+                                    const float* scale_host, float* member_traj, float* mean, float* spread,
+                                    double* scores) {
+  const std::string fn = "smaml_forecast_rollout_ensemble: ";
+  // (the checks that need no context first: they run without a device too)
+  if (!member_traj && !mean && !spread && !scores)
+    return fail(SMAML_EINVAL, fn + "member_traj, mean, spread and scores are all NULL (nothing to compute)");
+  if (norig <= 0 || batch <= 0 || !origins_host) return fail(SMAML_EINVAL, fn + "norig and batch must be positive");
+  if (members < 1 || members > 64)
+    return fail(SMAML_EINVAL, fn + "members must be in 1..64, got " + std::to_string(members));
+  if (cycles < 1 || cycles > RENS_MAX_CYCLES)
+    return fail(SMAML_EINVAL, fn + "cycles must be in 1.." + std::to_string(RENS_MAX_CYCLES) +
+                                  " (the mask site's step 64 j + e has 16 bits), got " + std::to_string(cycles));
+  if (!(p_gcn >= 0.f && p_gcn < 1.f) || !(p_lstm >= 0.f && p_lstm < 1.f))
+    return fail(SMAML_EINVAL, fn + "dropout probabilities must be in [0, 1)");
+  if (gap != 0 && gap != 1)
+    return fail(SMAML_EINVAL, fn + "gap must be 0 (persistence) or 1 (midpoint), got " + std::to_string(gap));
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_forecast_rollout_ensemble"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!theta || !aligned16(theta)) return fail(SMAML_EINVAL, fn + "theta must be a 16-byte aligned device pointer");
+  if (task < 0 || task >= (int)c->feats.size()) return fail(SMAML_EINVAL, fn + "task out of range");
+  const Dims& d = c->d;
+  const int sl = d.Hf + 1, R = cycles, E = members, Bmax = std::min(batch, norig);
+  if ((int64_t)d.T * Bmax * d.N * 4 * d.H >= (1ll << 30))
+    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^30");
+  const int64_t tt = c->t_total[task];
+  const int64_t need_in = d.T + (int64_t)(R - 1) * sl, need_sc = d.T + (int64_t)R * sl;
+  for (int i = 0; i < norig; ++i) {
+    const int64_t o = origins_host[i];
+    if (o < 0 || o + need_in > tt || (scores && o + need_sc > tt))
+      return fail(SMAML_EINVAL, fn + "origin " + std::to_string(i) + " (start " + std::to_string(o) +
+                                    (scores && o >= 0 && o + need_in <= tt ? ") has no targets for " : ") does not fit ") +
+                                    std::to_string(R) + " cycles in the stream of " + std::to_string(tt) + " steps");
+  }
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  hipStream_t s = (hipStream_t)stream;
+  const bool shared = p_gcn == 0.f;
+  RensPlan p{};
+  p.R = R;
+  p.gap = gap;
+  p.E = E;
+  p.Bmax = Bmax;
+  p.Btail = norig % batch ? norig % batch : Bmax;
+  p.S = d.T;
+  p.p_gcn = p_gcn;
+  p.p_lstm = p_lstm;
+  p.seed = seed;
+  p.norig = norig;
+  p.reuse = c->roll_reuse != 0;
+  p.fused = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  // members per launch set: option ens_group, else as many as fit the budget (at least one)
+  if (c->ens_group > 0) p.G = std::min(c->ens_group, E);
+  else if (c->ens_group == 0) p.G = E;
+  else
+    p.G = (int)std::max<int64_t>(
+        1, std::min<int64_t>(E, (c->roll_ens_budget_mb << 20) / rens_member_bytes(d, Bmax, R, !shared)));
+  const int G = p.G;
+  // every buffer at the largest pass's and group's size before the first launch, so no table entry can dangle
+  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = need_in, nrun_max = std::max(d.T - 1, 1);
+  const int64_t blkf = (int64_t)sl * d.N * d.C;
+  // (the per-layer chain's ping-pong buffers: a chunk of samples below 2^28 floats, or one member's T-row window)
+  const int64_t crows = p.fused ? 1 : nrun_max;  // (the fused stack takes the runs: only the t = 0 rows chain)
+  const int64_t chain = shared ? std::min<int64_t>((int64_t)G * Mx * crows * d.Hc,
+                                                   std::max<int64_t>(1ll << 28, crows * d.N * d.Hc))
+                               : (int64_t)d.T * Mx * d.Hc;
+  if (c->re_seq.grow((int64_t)G * Bmax * seq_rows * d.N * d.Cin0 * 4) != hipSuccess ||
+      (shared && c->re_xg.grow((int64_t)(p.S + 1) * G * Mx * 4 * d.H * 4) != hipSuccess) ||
+      (shared && c->re_obs.grow((int64_t)(d.T + 1) * Mx * 4 * d.H * 4) != hipSuccess) ||
+      (shared && c->re_F0.grow((int64_t)G * Mx * d.Hc * 4) != hipSuccess) ||
+      c->fc_F.grow((shared ? nrun_max : (int64_t)d.T) * G * Mx * d.Hc * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, chain * 4}, {&c->fc_gcnB, chain * 4}}) != hipSuccess ||
+      c->ens_ring.grow(2 * infer_ring_floats(d, G, (int)Mx) * 4) != hipSuccess ||
+      c->ens_pred.grow((int64_t)G * Mx * d.HfC * 4) != hipSuccess ||
+      (!member_traj && c->re_traj.grow((int64_t)E * Bmax * R * blkf * 4) != hipSuccess) ||
+      (scores && c->fc_part.grow((int64_t)skill_blocks(d, Bmax) * R * sl * d.C * 4 * 4) != hipSuccess) ||
+      (shared && p.fused && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the ensemble-rollout buffers failed (batch " + std::to_string(Bmax) + ", " +
+                                  std::to_string(R) + " cycles, " + std::to_string(G) + " members at a time)");
+  const int64_t rowf = (int64_t)d.N * d.Cin0;
+  const int nset = p.Btail != Bmax ? 2 : 1;
+  std::vector<const float*> ptrs((size_t)2 * norig + (size_t)R * 2 * G * (Bmax + (nset == 2 ? p.Btail : 0)));
+  for (int i = 0; i < norig; ++i) {
+    ptrs[i] = c->feats[task] + (int64_t)origins_host[i] * rowf;
+    ptrs[(size_t)norig + i] = ptrs[i] + rowf;
+  }
+  p.tab_src = 0;
+  p.tab_obs = norig;
+  const float* seq = c->re_seq.as<float>();
+  int64_t at = 2 * (int64_t)norig;
+  for (int k = 0; k < nset; ++k) {
+    const int B = k == 0 ? Bmax : p.Btail;
+    p.tab_cyc[k] = at;
+    for (int j = 0; j < R; ++j)
+      for (int zb = 0; zb < G * B; ++zb) {
+        const float* sb = seq + (int64_t)zb * seq_rows * rowf;
+        ptrs[(size_t)(at + ((int64_t)j * 2) * G * B + zb)] = sb + (int64_t)j * sl * rowf;
+        ptrs[(size_t)(at + ((int64_t)j * 2 + 1) * G * B + zb)] = sb + (int64_t)roll_run_first(j, d.T, sl, p.reuse) * rowf;
+      }
+    at += (int64_t)R * 2 * G * B;
+  }
+  for (auto& x : c->re_stats) x = 0;
+  const Work saved = c->w;
+  const int act = c->act_B;
+  auto run = [&]() -> int {
+    const float* scale_dev = nullptr;
+    if (scores && scale_host) {
+      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
+      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
+      scale_dev = c->fc_scale.as<float>();
+    }
+    TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
+    for (int64_t done = 0; done < norig; done += batch)
+      TRY(rens_pass(c, s, theta, p, done, (int)std::min<int64_t>(batch, norig - done), scale_dev, member_traj,
+                    mean, spread, scores));
+    return SMAML_OK;
+  };
+  const int rc = run();
+  c->w = saved;
+  c->act_B = act;
+  return rc;
+}
+
+int smaml_rollout_ensemble_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad rollout_ensemble_stats arguments");
+  for (int i = 0; i < 7 && i < cap; ++i) counts[i] = c->re_stats[i];
+  if (count) *count = 7;
   return SMAML_OK;
 }
 
@@ -3014,6 +3414,8 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->ens_share = (int)value;
   } else if (k == "ens_group" && value >= -1 && value <= 64) {
     c->ens_group = (int)value;
+  } else if (k == "roll_ens_budget_mb" && value >= 1 && value <= (1 << 20)) {
+    c->roll_ens_budget_mb = value;
   } else if (k == "dx0_fused" && (value == 0 || value == 1)) {
     c->dx0_fused = (int)value;
   } else if (k == "gcn_keep" && (value == 0 || value == 1)) {

@@ -224,6 +224,8 @@ struct XgDedup {
   // rho % ring_S, so step t >= 1 of the cycle whose window starts at private row ring_r0 reads the block of
   // slot (ring_r0 + t) % ring_S, and step 0 reads xg0 [M][4H] (its features see the graph: recomputed per
   // cycle). Both blocks are linear in the tile row m, as the consecutive-window mode's are.
+  // k_lstm_fwd_infer_drop (smaml_forecast_rollout_ensemble) reads the same mode over its member axis, with the
+  // table slot-major over the group's members and ring_r0 unused: see EnsDrop.
   const float* xg0 = nullptr;
   int ring_S = 0, ring_r0 = 0;
 };
@@ -461,13 +463,15 @@ struct RollArgs {
   int seq_rows = 0;                  // T + (R - 1)(Hf + 1)
 };
 // seq[b][rho] = src[b][rho] for rho < T (all channels)
-void launch_rollout_init(hipStream_t s, const RollArgs& a);
+// (G > 1: the ensemble rollout's members, grid z; member z's sequences at seq + (z B + b) seq_stride)
+void launch_rollout_init(hipStream_t s, const RollArgs& a, int G = 1);
 // Cycle j's appended rows from pred [B][N*Hf][C] (F4 view [Hf][N][C]): the s = Hf + 1 rows at rho0 = j s + T
 // (gap row, then the Hf predicted rows; channels >= C from the stream row of the same time) into the
 // sequences when `store_seq` (not on the last cycle: nothing reads them), and their weather channels into
 // out + b * out_stride [s][N][C] (the cycle's traj block, or a scratch the skill sums read).
+// G members (grid z): pred [G][B][N*Hf][C], sequences as launch_rollout_init's, out + z * out_zstride.
 void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, bool store_seq, const float* pred,
-                           float* out, int64_t out_stride);
+                           float* out, int64_t out_stride, int G = 1, int64_t out_zstride = 0);
 // Skill sums of cycle j's s leads from blk + b * blk_stride [s][N][C]: f32 partials per block into part
 // [rollout_skill_blocks][s C][3], added in double onto skill [3][R s][C] at leads j s .. j s + s - 1 (first:
 // overwritten). launch_skill_sums's scheme: fixed order, no atomics.
@@ -504,6 +508,13 @@ struct EnsDrop {
   int e0 = 0;        // member of z = 0
   int64_t row0 = 0, Mtot = 0;
   int share0 = 0;    // layer 0 computed by z = 0 only and read by every member (no mask below its output)
+  // smaml_forecast_rollout_ensemble (XgDedup::ring_S > 0; e0 = 64 j + the first member): the cycle's window
+  // starts at private row ring_row; rows below obs_rows are observed, the same in every member, and their
+  // projection lives once in xg_obs [obs_rows][M][4H]; the others in member z's slots of XgDedup::xg
+  // [ring_S][G][M][4H]; the t = 0 block of member z is xg0_z floats past XgDedup::xg0 (0: one for all)
+  const float* xg_obs = nullptr;
+  int obs_rows = 0, ring_row = 0;
+  int64_t xg0_z = 0;
 };
 // G members' diagonal on rings [L][2][G][M][H]; member z's features fz floats past w.F (0: shared, then the
 // XG table of w.xgd applies)
@@ -519,6 +530,13 @@ hipError_t ens_stats_prepare();  // raise k_ens_stats's dynamic-LDS limit on the
 void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P, const float* const* xtab,
                       const float* scale, float* mean, float* spread, float* member_pred, int64_t mstride, float* part,
                       double* scores, bool first);
+// Ensemble-rollout statistics of one pass (k_rens_stats): X [E][B][Q][N][C] (Q = R (Hf + 1) trajectory rows per
+// origin, member stride estride) against src[b] = the origin's stream rows; mean / spread [B][Q][N][C]; part
+// [skill_blocks][Q C][4] f32 partials, added in double onto scores [4][Q][C] (first: overwritten).
+hipError_t rens_stats_prepare();  // as ens_stats_prepare, for k_rens_stats
+void launch_rens_stats(hipStream_t s, const Dims& d, int B, int E, int Q, const float* X, int64_t estride,
+                       const float* const* src, const float* scale, float* mean, float* spread, float* part,
+                       double* scores, bool first);
 // launch_head_loss's prediction alone from given h_T rows (hz floats between tasks) into pred [Z][M][HfC]
 void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
                       int64_t tstride, const ParamOff& po, float* pred);

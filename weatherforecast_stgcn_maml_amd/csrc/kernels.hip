@@ -632,6 +632,15 @@ __global__ SMAML_GATE_ATTR __launch_bounds__(CfgGate::NTH) void k_lstm_fwd_infer
   Acc<CfgGate> acc;
   acc.zero();
   const float* xgt = xd.xg && l == 0 ? xd.xg + xg_dedup_row0(t, M, xd.N) * (4 * H) : nullptr;
+  // slot-table mode (XgDedup::ring_S, the ensemble rollout): step 0 reads member z's t = 0 block, step t >= 1
+  // private row ed.ring_row + t -- an observed row (< ed.obs_rows) from the table all members share, an
+  // appended one from member z's slot of the table [ring_S][Z][M][4H]
+  if (xgt && xd.ring_S > 0) {
+    const int rho = ed.ring_row + t;
+    xgt = t == 0                ? xd.xg0 + (int64_t)z * ed.xg0_z
+          : rho < ed.obs_rows ? ed.xg_obs + (int64_t)rho * M * (4 * H)
+                              : xd.xg + ((int64_t)(rho % xd.ring_S) * Z + z) * M * (4 * H);
+  }
   const int kbeg = xgt ? cin : 0;
   const float* X = l > 0 ? at(ringH, l - 1, t) : xgt ? F : F + (int64_t)z * fz + (int64_t)t * M * cin;
   const XDrop xdm{drop_site(ed.seed, 2, ed.e0 + z, l > 0 ? l - 1 : 0), ed.thr, ed.sc,
@@ -1512,19 +1521,21 @@ void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, c
 // ---- autoregressive rollout (smaml_forecast_rollout) ------------------------------------------------
 // Origin b (blockIdx.y) keeps a private sequence X = a.seq + b a.seq_stride, rows [seq_rows][N][Cin]; its
 // stream rows are a.src[b] = S + o_b N Cin, so S[o_b + rho] is row rho of a.src[b].
+// The grid's z axis is the ensemble member (smaml_forecast_rollout_ensemble; one member otherwise): member z's
+// sequences follow member z - 1's B, and every member starts from the same stream rows.
 __global__ void k_rollout_init(RollArgs a) {
   const int b = blockIdx.y;
   const int64_t n4 = (int64_t)a.T * a.N * a.Cin / 4;  // (Cin % 4 == 0, both 16-byte aligned)
   const float4* src = reinterpret_cast<const float4*>(a.src[b]);
-  float4* dst = reinterpret_cast<float4*>(a.seq + (int64_t)b * a.seq_stride);
+  float4* dst = reinterpret_cast<float4*>(a.seq + ((int64_t)blockIdx.z * a.B + b) * a.seq_stride);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
     dst[i] = src[i];
 }
 
-void launch_rollout_init(hipStream_t s, const RollArgs& a) {
+void launch_rollout_init(hipStream_t s, const RollArgs& a, int G) {
   const int64_t n4 = (int64_t)a.T * a.N * a.Cin / 4;
   const unsigned gx = (unsigned)std::min<int64_t>((n4 + 255) / 256, 256);
-  k_rollout_init<<<dim3(gx, (unsigned)a.B), 256, 0, s>>>(a);
+  k_rollout_init<<<dim3(gx, (unsigned)a.B, (unsigned)G), 256, 0, s>>>(a);
 }
 
 // One thread per element (i, n, c) of the cycle's s = Hf + 1 appended rows, rho = rho0 + i, rho0 = j s + T:
@@ -1534,22 +1545,23 @@ void launch_rollout_init(hipStream_t s, const RollArgs& a) {
 //   i >= 1: P[i - 1][n][c], P = the flat prediction [N Hf][C] of origin b read as [Hf][N][C] (F4): a copy.
 // Row rho0 - 1 was written by the previous cycle (or is an observed row): no thread of this launch writes it.
 // The weather channels of stream rows >= o + T are never read. Plain 4-byte accesses: C need not be a
-// multiple of 4.
+// multiple of 4. Grid z = ensemble member (one otherwise): member z's sequences and predictions follow member
+// z - 1's B, its output blocks are out_zstride floats on.
 __global__ void k_rollout_append(RollArgs a, int rho0, int gap, int store_seq, const float* __restrict__ pred,
-                                 float* __restrict__ out, int64_t out_stride) {
-  const int b = blockIdx.y, s = a.Hf + 1;
+                                 float* __restrict__ out, int64_t out_stride, int64_t out_zstride) {
+  const int b = blockIdx.y, s = a.Hf + 1, zb = (int)blockIdx.z * a.B + b;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)s * a.N * a.Cin) return;
   const int c = (int)(e % a.Cin);
   const int64_t in = e / a.Cin;
   const int n = (int)(in % a.N), i = (int)(in / a.N);
-  float* X = a.seq + (int64_t)b * a.seq_stride;
+  float* X = a.seq + (int64_t)zb * a.seq_stride;
   const int64_t at = ((int64_t)(rho0 + i) * a.N + n) * a.Cin + c;
   if (c >= a.C) {
     if (store_seq) X[at] = a.src[b][at];
     return;
   }
-  const float* P = pred + (int64_t)b * a.N * a.Hf * a.C;
+  const float* P = pred + (int64_t)zb * a.N * a.Hf * a.C;
   float v;
   if (i == 0) {
     const float prev = X[((int64_t)(rho0 - 1) * a.N + n) * a.Cin + c];
@@ -1558,14 +1570,14 @@ __global__ void k_rollout_append(RollArgs a, int rho0, int gap, int store_seq, c
     v = P[((int64_t)(i - 1) * a.N + n) * a.C + c];
   }
   if (store_seq) X[at] = v;
-  out[(int64_t)b * out_stride + ((int64_t)i * a.N + n) * a.C + c] = v;
+  out[(int64_t)blockIdx.z * out_zstride + (int64_t)b * out_stride + ((int64_t)i * a.N + n) * a.C + c] = v;
 }
 
 void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, bool store_seq, const float* pred,
-                           float* out, int64_t out_stride) {
+                           float* out, int64_t out_stride, int G, int64_t out_zstride) {
   const int64_t n = (int64_t)(a.Hf + 1) * a.N * a.Cin;
-  k_rollout_append<<<dim3((unsigned)((n + 255) / 256), (unsigned)a.B), 256, 0, s>>>(
-      a, j * (a.Hf + 1) + a.T, gap, store_seq ? 1 : 0, pred, out, out_stride);
+  k_rollout_append<<<dim3((unsigned)((n + 255) / 256), (unsigned)a.B, (unsigned)G), 256, 0, s>>>(
+      a, j * (a.Hf + 1) + a.T, gap, store_seq ? 1 : 0, pred, out, out_stride, out_zstride);
 }
 
 // Skill sums of one cycle: k_skill_part's scheme per (row i of the cycle, variable c) -- block (i C + c, k)
@@ -1725,6 +1737,91 @@ void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P
   k_ens_stats<<<dim3(d.HfC, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
       P, E, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, mean, spread, member_pred, mstride, scores ? part : nullptr);
   if (scores) k_ens_final<<<(4 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, scores, first ? 1 : 0);
+}
+
+// ---- ensemble-rollout statistics (smaml_forecast_rollout_ensemble) ------------------------------------
+// k_ens_stats's scheme over the trajectory layout: X [E][B][R s][N][C] (member stride estride) holds the
+// pass's members, row q = j s + i of an origin being row i of cycle j (the gap row included). Block (q C + c, k)
+// takes the (origin, node) pairs [k SKILL_PAIRS, (k + 1) SKILL_PAIRS): per element the mean and spread as in
+// k_ens_stats (double, rounded once) into mean / spread [B][R s][N][C], and with `part` the four f32 block
+// partials against y = S[o + T + q][n][c] and y_last = S[o + T - 1][n][c] (src[b] = S + o_b N Cin). Rows are
+// [N][C] already: no F4 pairing here.
+__global__ __launch_bounds__(NT) void k_rens_stats(const float* __restrict__ X, int64_t estride, int E,
+                                                   const float* const* __restrict__ src,
+                                                   const float* __restrict__ scale, int B, int N, int Q, int C, int T,
+                                                   int yld, float* __restrict__ mean, float* __restrict__ spread,
+                                                   float* __restrict__ part) {
+  extern __shared__ float xs[];  // [E][NT]
+  __shared__ float red[NT / 64];
+  const int qc = blockIdx.x, q = qc / C, c = qc - q * C;
+  const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, B * N);
+  const float sc = scale ? scale[c] : 1.f;
+  const float invE = 1.f / (float)E;
+  float se = 0.f, sv = 0.f, sr = 0.f, pe = 0.f;
+  float* col = xs + threadIdx.x;
+  for (int p = p0 + (int)threadIdx.x; p < p1; p += NT) {
+    const int b = p / N, n = p - b * N;
+    const int64_t idx = (((int64_t)b * Q + q) * N + n) * C + c;
+    double sum = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const float x = X[(int64_t)e * estride + idx];
+      col[e * NT] = x;
+      sum += (double)x;
+    }
+    const double mud = sum / (double)E;
+    const float mu = (float)mud;
+    double ss = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const double dv = (double)col[e * NT] - mud;
+      ss = fma(dv, dv, ss);
+    }
+    const float var = E > 1 ? (float)(ss / (double)(E - 1)) : 0.f;
+    if (mean) mean[idx] = mu;
+    if (spread) spread[idx] = sqrtf(var);
+    if (part) {
+      const float* xw = src[b];
+      const float y = xw[((int64_t)(T + q) * N + n) * yld + c];
+      const float yl = xw[((int64_t)(T - 1) * N + n) * yld + c];
+      float ae = 0.f, pw = 0.f;
+      for (int i = 0; i < E; ++i) {
+        const float xi = col[i * NT];
+        ae += fabsf(xi - y);
+        for (int j = i + 1; j < E; ++j) pw += fabsf(xi - col[j * NT]);
+      }
+      const float crps = ae * invE - pw * invE * invE;
+      const float em = sc * (mu - y), qq = sc * (yl - y);
+      se = fmaf(em, em, se);
+      sv = fmaf(sc * sc, var, sv);
+      sr = fmaf(sc, crps, sr);
+      pe = fmaf(qq, qq, pe);
+    }
+  }
+  if (!part) return;
+  float* o = part + ((int64_t)blockIdx.y * gridDim.x + qc) * 4;
+  const float s0 = block_sum(se, red);
+  const float s1 = block_sum(sv, red);
+  const float s2 = block_sum(sr, red);
+  const float s3 = block_sum(pe, red);
+  if (threadIdx.x == 0) {
+    o[0] = s0;
+    o[1] = s1;
+    o[2] = s2;
+    o[3] = s3;
+  }
+}
+
+// (k_ens_final adds the blocks in order in double onto scores [4][Q][C]: the same layout with HfC = Q C)
+hipError_t rens_stats_prepare() {
+  return hipFuncSetAttribute((const void*)k_rens_stats, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+}
+
+void launch_rens_stats(hipStream_t s, const Dims& d, int B, int E, int Q, const float* X, int64_t estride,
+                       const float* const* src, const float* scale, float* mean, float* spread, float* part,
+                       double* scores, bool first) {
+  const int nblk = skill_blocks(d, B);
+  k_rens_stats<<<dim3(Q * d.C, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+      X, estride, E, src, scale, B, d.N, Q, d.C, d.T, d.Cin0, mean, spread, scores ? part : nullptr);
+  if (scores) k_ens_final<<<(4 * Q * d.C + 127) / 128, 128, 0, s>>>(part, nblk, Q * d.C, scores, first ? 1 : 0);
 }
 
 // ====================================================================================

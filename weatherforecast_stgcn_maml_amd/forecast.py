@@ -449,3 +449,144 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
                               p_lstm)
     rmse, rms, ratio, crps, prmse = ensemble_metrics(sums.cpu().numpy(), int(w.size) * N, E)
     return EnsembleResult(mean_o, spread_o, mem_o, rmse, rms, ratio, crps, prmse, int(w.size), E, w, seed, p_gcn, p_lstm)
+
+
+# ---- ensemble rollout (smaml_forecast_rollout_ensemble) -------------------------------------------------
+# Every MC-dropout member feeds its OWN forecast back in: how the spread grows with lead time, and whether it
+# keeps pace with the error of the ensemble mean. Cycle j of member e runs under the masks of step 64 j + e, so
+# cycle 0 is ``ensemble_forecast``'s member e and a member does not depend on E, R or the pass size.
+def ensemble_rollout_reference(member_traj, features, origins: Sequence[int], dims, scale=None):
+    """``(mean, spread, sums)`` in float64 of the member trajectories ``member_traj [E, norig, R s, N, C]``
+    (normalised; any shape that reshapes to it): ``mean`` / ``spread [norig, R s, N, C]`` -- the member mean and
+    the unbiased standard deviation about it (0 at E = 1) -- and ``sums [4, R s, C]`` (order ``ENSEMBLE_SUMS``) per
+    absolute lead ``k`` and variable over origins and nodes, every row (gap rows included) against
+    ``y = features[o + T + k]`` and the persistence ``y_last = features[o + T - 1]``: ``sum (s (mu - y))^2``,
+    ``sum s^2 sigma^2``, ``sum s CRPS`` with ``CRPS = (1/E) sum_i |x_i - y| - (1/(2 E^2)) sum_ij |x_i - x_j|``,
+    ``sum (s (y_last - y))^2``. Rows are ``[N, C]`` already: no F4 pairing. Pure numpy; needs no GPU."""
+    T, N, C = dims.window_size, dims.num_nodes, dims.output_channels
+    x = np.asarray(member_traj, np.float64)
+    E, norig = x.shape[0], len(origins)
+    x = x.reshape(E, norig, -1, N, C)
+    K = x.shape[2]
+    mean = x.sum(axis=0) / E
+    var = ((x - mean) ** 2).sum(axis=0) / (E - 1) if E > 1 else np.zeros_like(mean)
+    f = np.asarray(features)
+    s = np.ones(C) if scale is None else np.asarray(scale, np.float64).reshape(C)
+    sums = np.zeros((4, K, C))
+    for i, o in enumerate(origins):
+        o = int(o)
+        if o < 0 or o + T + K > f.shape[0]:
+            raise ValueError(f"origin {o} has no targets for {K} leads in a stream of {f.shape[0]} steps")
+        y = f[o + T:o + T + K, :, :C].astype(np.float64)
+        y_last = f[o + T - 1, :, :C].astype(np.float64)[None]
+        xi = x[:, i]
+        crps = np.abs(xi - y).sum(axis=0) / E - np.abs(xi[:, None] - xi[None, :]).sum(axis=(0, 1)) / (2.0 * E * E)
+        sums[0] += (((mean[i] - y) * s) ** 2).sum(axis=1)
+        sums[1] += (var[i] * s * s).sum(axis=1)
+        sums[2] += (crps * s).sum(axis=1)
+        sums[3] += (((y_last - y) * s) ** 2).sum(axis=1)
+    return mean, np.sqrt(var), sums
+
+
+def ensemble_rollout_metrics(sums: np.ndarray, count: int):
+    """(rmse of the mean, rms spread, spread-skill ratio ``rms_spread / rmse``, mean CRPS, persistence rmse, skill
+    ``1 - mean_sse / persistence_sse``) ``[R s, C]`` from the sums ``[4, R s, C]`` over ``count`` (origin, node)
+    pairs per entry; the ratios are NaN where their denominator is 0."""
+    sums = np.asarray(sums, np.float64)
+    rmse, rms = np.sqrt(sums[0] / count), np.sqrt(sums[1] / count)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(sums[0] > 0, rms / rmse, np.nan)
+        skill = np.where(sums[3] > 0, 1.0 - sums[0] / sums[3], np.nan)
+    return rmse, rms, ratio, sums[2] / count, np.sqrt(sums[3] / count), skill
+
+
+@dataclass
+class EnsembleRolloutResult:
+    mean: Optional[np.ndarray]              # [norig, R s, N, C], physical units over the first len(std) variables
+    spread: Optional[np.ndarray]            # [norig, R s, N, C], physical units (spread * std)
+    members: Optional[np.ndarray]           # [E, norig, R s, N, C] with return_members
+    is_gap: np.ndarray                      # [R s] bool: the rows no forecast covers (filled by the gap rule)
+    rmse: Optional[np.ndarray]              # [R s, C] per absolute lead: of the ensemble mean
+    rms_spread: Optional[np.ndarray]        # [R s, C]
+    spread_skill: Optional[np.ndarray]      # [R s, C]: rms_spread / rmse
+    crps: Optional[np.ndarray]              # [R s, C]: mean CRPS
+    persistence_rmse: Optional[np.ndarray]  # [R s, C]
+    skill: Optional[np.ndarray]             # [R s, C]: 1 - SSE(mean) / SSE_persistence
+    n_origins: int
+    n_members: int
+    origins: np.ndarray
+    cycles: int
+    gap: str
+    seed: int
+    p_gcn: float
+    p_lstm: float
+
+
+def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, members: int = 16,
+                     p_gcn=None, p_lstm=None, seed=None, gap="midpoint", batch: int = 32, score: bool = True,
+                     return_members: bool = False, ctx=None) -> EnsembleRolloutResult:
+    """``rollout`` for an MC-dropout ensemble (``smaml_forecast_rollout_ensemble``): each of the ``members`` feeds
+    its own forecast back in for ``cycles`` x ``(Hf + 1)`` steps, member ``e`` of cycle ``j`` under the library's
+    masks of ``(seed, step 64 j + e)``. Defaults as ``ensemble_forecast`` (the model's own dropout rates,
+    ``draw_dropout_seed()``) and ``rollout`` (``rollout_origins``; ``extend_stream`` with ``score=False`` to forecast
+    past the last observation). Returns the ensemble mean and spread along the trajectory in physical units,
+    optionally every member, and with ``score`` the metrics of ``ensemble_rollout_metrics`` per absolute lead and
+    variable (count per lead: ``norig * N``).
+
+    Cost: with ``p_gcn == 0`` the observed rows' GCN features and projection are computed once per pass for all
+    members and cycle 0 shares LSTM layer 0; ``p_gcn > 0`` recomputes every member's whole window each cycle on
+    the per-layer kernels (correct, not tuned). Pass ``p_gcn=0.0`` for LSTM-only MC dropout."""
+    import torch
+
+    from . import _capi
+    from .hybrid_model import draw_dropout_seed
+    from .model import _set_graph
+
+    g = _gap_code(gap)
+    R, E = int(cycles), int(members)
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _capi.SmamlError(-1, "ensemble_rollout runs on a HIP device only")
+    p_gcn = float(model.base_stgcn.dropout.p) if p_gcn is None else float(p_gcn)
+    p_lstm = float(model.dropout.p) if p_lstm is None else float(p_lstm)
+    seed = draw_dropout_seed() if seed is None else int(seed) & 0xFFFFFFFF
+    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
+    f = f.to(dev, torch.float32).contiguous()
+    T = model.base_stgcn.window_size
+    Hf, C = model.forecast_horizon, model.out_channels
+    s = Hf + 1
+    t_total, N = int(f.shape[0]), int(f.shape[1])
+    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
+    is_gap = (np.arange(R * s) % s) == 0
+    gname = "midpoint" if g else "persistence"
+    tail = (int(o.size), E, o, R, gname, seed, p_gcn, p_lstm)
+    if o.size == 0:
+        return EnsembleRolloutResult(None, None, None, is_gap, None, None, None, None, None, None, *tail)
+    if ctx is None:
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+    else:
+        dims = model.dims(N)
+        _set_graph(ctx, ei)
+        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
+        ctx.set_gcn_params(gflat)
+        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
+    ctx.set_tasks([f])
+    mean_s, std = _stats(stats, C)
+    mean = torch.empty(o.size, R, s, N, C, device=dev)
+    spread = torch.empty(o.size, R, s, N, C, device=dev)
+    mem = torch.empty(E, o.size, R, s, N, C, device=dev) if return_members else None
+    sums = torch.empty(4, R * s, C, device=dev, dtype=torch.float64) if score else None
+    with torch.no_grad():
+        ctx.forecast_rollout_ensemble(_capi.stream_ptr(torch), theta, o, batch, R, E, p_gcn, p_lstm, seed, gap=g,
+                                      scale=std if score else None, member_traj=mem, mean=mean, spread=spread,
+                                      scores=sums)
+        scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
+        shift_t = torch.from_numpy(mean_s.astype(np.float32)).to(dev)
+        mean_o = (mean * scale_t + shift_t).view(o.size, R * s, N, C).cpu().numpy()
+        spread_o = (spread * scale_t).view(o.size, R * s, N, C).cpu().numpy()
+        mem_o = (mem * scale_t + shift_t).view(E, o.size, R * s, N, C).cpu().numpy() if mem is not None else None
+    if not score:
+        return EnsembleRolloutResult(mean_o, spread_o, mem_o, is_gap, None, None, None, None, None, None, *tail)
+    rmse, rms, ratio, crps, prmse, skill = ensemble_rollout_metrics(sums.cpu().numpy(), int(o.size) * N)
+    return EnsembleRolloutResult(mean_o, spread_o, mem_o, is_gap, rmse, rms, ratio, crps, prmse, skill, *tail)
