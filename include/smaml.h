@@ -82,9 +82,30 @@ int smaml_param_layout(const smaml_dims* dims, int32_t which, int64_t* offsets, 
  * edge_index of graphBuilder.build_spatial_graph (graphBuilder.py:9-47). Any edge_index with
  * in-degree <= 7 (self loops not counted) is accepted: parallel edges count twice, self loops in the
  * input are replaced by the one every node gets, isolated nodes keep that loop alone (weight 1), the
- * edge order is free. A source or target outside [0, num_nodes) or an in-degree of 8: SMAML_EINVAL. */
+ * edge order is free. A source or target outside [0, num_nodes) or an in-degree of 8: SMAML_EINVAL
+ * (smaml_graph_csr / smaml_set_graph_weighted take such graphs, and edge weights). */
 int smaml_graph_ell(const int64_t* edge_index_host, int64_t num_edges, int32_t num_nodes,
                     int32_t* cols_host, float* vals_host);
+
+/* The same adjacency as CSR, for any in-degree and optional edge weights (PyG 2.x gcn_norm with edge_weight;
+ * host-only, the twin of smaml_graph_ell). edge_index [2, E] (sources, then targets), edge_weight [E] or NULL
+ * (all ones):
+ *  - an edge s -> t with s != t adds an entry of weight w_e to row t; parallel edges stay separate entries, so
+ *    their contributions add;
+ *  - self loops in the input are removed and every node gets one loop (add_remaining_self_loops): its weight is
+ *    that of the LAST input entry (i, i) in edge order, 1 if there is none (NULL weights: always 1);
+ *  - deg[t] = loop[t] + the sum of t's in-edge weights, summed in double in edge order, rounded once to float;
+ *    dinv[t] = 1.f / sqrtf(deg[t]), 0 where deg[t] is 0; an entry's value is (dinv[s] * w) * dinv[t] in float;
+ *  - row t holds its in-edges in input order, then its self loop; entries of value 0 (zero weights, anything
+ *    touching a node of degree 0) are dropped. With NULL weights and in-degree <= 7 the rows are the ELL's
+ *    non-padding columns and values, bit for bit.
+ * SMAML_EINVAL, with a message naming the edge, before anything is written: an index outside [0, num_nodes), a
+ * negative, NaN or infinite weight, more than 2^31 - 1 entries. rowptr_host [num_nodes + 1]; cols_host / vals_host
+ * hold cap entries. *nnz_out is always written (0 if the graph is rejected); cap < *nnz_out: SMAML_EINVAL, with
+ * rowptr, cols and vals untouched. */
+int smaml_graph_csr(const int64_t* edge_index_host, const float* edge_weight_host, int64_t num_edges,
+                    int32_t num_nodes, int32_t* rowptr_host, int32_t* cols_host, float* vals_host, int64_t cap,
+                    int64_t* nnz_out);
 
 /* ---- context ----------------------------------------------------------------------- */
 int smaml_create(const smaml_dims* dims, int32_t device, smaml_ctx** out);
@@ -92,6 +113,19 @@ int smaml_destroy(smaml_ctx* ctx);
 
 /* Upload the graph (edge_index [2, E] int64, host). */
 int smaml_set_graph(smaml_ctx* ctx, const int64_t* edge_index_host, int64_t num_edges);
+
+/* Upload the graph in its general form (smaml_graph_csr's rules: any in-degree, edge_weight_host [E] or NULL):
+ * A_hat and A_hat^T as CSR. It replaces the context's graph exactly as smaml_set_graph does (the adaptation
+ * feature cache is dropped, pending state stays as valid as it was) and every entry point that reads the graph
+ * honours it; a later smaml_set_graph switches back to the ELL, and the other way round. A call of either that
+ * fails leaves the live graph as it was. On a graph both accept the two forms give the same bits. */
+int smaml_set_graph_weighted(smaml_ctx* ctx, const int64_t* edge_index_host, const float* edge_weight_host,
+                             int64_t num_edges);
+
+/* Host counters of the live graph (cap entries written, *count = 5): [0] form (0 none, 1 ELL, 2 CSR), [1] entries
+ * of A_hat, [2] its longest row, and since the graph was set: [3] k_gcn_layer launches that gathered through the
+ * CSR, [4] k_gather_rows / k_gcn_dz launches that read a CSR of A_hat or A_hat^T of the CSR form. */
+int smaml_graph_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
 
 /* Frozen GCN parameters (flat, layout which=1), device pointer kept by reference. */
 int smaml_set_gcn_params(smaml_ctx* ctx, const float* gcn_flat);

@@ -390,6 +390,66 @@ int main() {
   CHECK(smaml_graph_ell(nullptr, 2, N, cols.data(), vals.data()) == SMAML_EINVAL);
   CHECK(smaml_graph_ell(ei.data(), E, 0, cols.data(), vals.data()) == SMAML_EINVAL);
 
+  // ---- the same adjacency as CSR (smaml_graph_csr: any in-degree, optional weights) ----
+  {
+    // the grid graph: the CSR rows are the ELL's non-zero entries, in order, bit for bit
+    std::vector<int32_t> rp((size_t)N + 1, -1), cc((size_t)E + N, -1);
+    std::vector<float> cv((size_t)E + N, -1.f);
+    int64_t nnz = -1;
+    CHECK(smaml_graph_ell(ei.data(), E, N, cols.data(), vals.data()) == 0);
+    CHECK(smaml_graph_csr(ei.data(), nullptr, E, N, rp.data(), cc.data(), cv.data(), E + N, &nnz) == 0);
+    CHECK(nnz == E + N && rp[0] == 0 && rp[N] == nnz);
+    for (int i = 0; i < N; ++i) {
+      int32_t e = rp[i];
+      for (int j = 0; j < W; ++j) {
+        if (vals[(size_t)i * W + j] == 0.f) continue;
+        CHECK(e < rp[i + 1] && cc[e] == cols[(size_t)i * W + j] &&
+              std::memcmp(&cv[e], &vals[(size_t)i * W + j], sizeof(float)) == 0);
+        ++e;
+      }
+      CHECK(e == rp[i + 1]);
+    }
+    // the star the ELL rejects, weighted; a zero weight, a weighted self loop given twice (the last one stays)
+    std::vector<int64_t> st;
+    for (int k = 1; k <= 8; ++k) st.push_back(k);
+    st.insert(st.end(), {0, 0});
+    for (int k = 1; k <= 8; ++k) st.push_back(0);
+    st.insert(st.end(), {0, 0});
+    std::vector<float> sw = {1.f, 2.f, 0.f, 4.f, 0.5f, 1.f, 1.f, 1.f, 0.25f, 3.f};
+    const int n = 9;
+    std::vector<int32_t> rp9((size_t)n + 1, -1);
+    CHECK(smaml_graph_csr(st.data(), sw.data(), 10, n, rp9.data(), cc.data(), cv.data(), 5, &nnz) == SMAML_EINVAL);
+    CHECK(nnz == 7 + n && rp9[0] == -1 && std::strstr(smaml_last_error(), "cap") != nullptr);  // nnz written, rowptr not
+    CHECK(smaml_graph_csr(st.data(), sw.data(), 10, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == 0);
+    CHECK(nnz == 16 && rp9[1] == 8 && cc[7] == 0);                          // 7 in-edges (the zero one dropped) + loop
+    const float deg0 = 3.f + 1.f + 2.f + 4.f + 0.5f + 1.f + 1.f + 1.f;      // loop 3 (the last) + the weights
+    CHECK(std::fabs(cv[7] - 3.f / deg0) < 1e-6f);
+    CHECK(cc[0] == 1 && cc[2] == 4 && std::fabs(cv[2] - 4.f / std::sqrt(deg0 * 1.f)) < 1e-6f);
+    double row0 = 0.0;
+    for (int e = rp9[0]; e < rp9[1]; ++e) row0 += cv[e];
+    CHECK(row0 > 0.0);
+    // rejections name the edge; *nnz_out is still written
+    for (float bad : {-1.f, NAN, INFINITY}) {
+      sw[4] = bad;
+      nnz = -1;
+      CHECK(smaml_graph_csr(st.data(), sw.data(), 10, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == SMAML_EINVAL);
+      CHECK(nnz == 0 && std::strstr(smaml_last_error(), "edge 4") != nullptr);
+    }
+    std::vector<int64_t> badcsr = {0, 1, 1, n};
+    CHECK(smaml_graph_csr(badcsr.data(), nullptr, 2, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == SMAML_EINVAL);
+    CHECK(std::strstr(smaml_last_error(), "edge 1") != nullptr);
+    badcsr = {-1, 0, 0, 1};
+    CHECK(smaml_graph_csr(badcsr.data(), nullptr, 2, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == SMAML_EINVAL);
+    CHECK(smaml_graph_csr(nullptr, nullptr, 2, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == SMAML_EINVAL);
+    CHECK(smaml_graph_csr(st.data(), nullptr, 10, n, rp9.data(), cc.data(), cv.data(), 16, nullptr) == SMAML_EINVAL);
+    // no edges: every row its loop of weight 1
+    CHECK(smaml_graph_csr(st.data(), nullptr, 0, n, rp9.data(), cc.data(), cv.data(), 16, &nnz) == 0);
+    CHECK(nnz == n && rp9[n] == n && cc[n - 1] == n - 1 && cv[0] == 1.f);
+    CHECK(smaml_set_graph_weighted(nullptr, st.data(), nullptr, 10) == SMAML_EINVAL);
+    int64_t gst[5];
+    CHECK(smaml_graph_stats(nullptr, gst, 5, nullptr) == SMAML_EINVAL);
+  }
+
   // ---- entry points on a NULL handle / without a device ----
   smaml_ctx* ctx = nullptr;
   const int rc = smaml_create(&d, 0, &ctx);

@@ -27,7 +27,8 @@ EXPORTS = (
     "smaml_adapt_prepare", "smaml_adapt_phases", "smaml_forecast", "smaml_forecast_bytes",
     "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
     "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
-    "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats",
+    "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats", "smaml_graph_csr", "smaml_set_graph_weighted",
+    "smaml_graph_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -144,6 +145,13 @@ _SIGS["smaml_rollout_ensemble_stats"] = ([P, PI64, I32, PI32], I32)
 ROLLOUT_ENSEMBLE_STATS = ("cycles", "member_rows", "shared_rows", "graph_rows", "xg_rows", "append_launches",
                           "member_groups")
 ROLLOUT_ENSEMBLE_MAX_CYCLES = 1024  # the mask site's step 64 j + e has 16 bits
+_SIGS["smaml_graph_csr"] = ([PI64, PF32, I64, I32, PI32, PI32, PF32, I64, PI64], I32)
+_SIGS["smaml_set_graph_weighted"] = ([P, PI64, PF32, I64], I32)
+_SIGS["smaml_graph_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_graph_stats order (host counters of the live graph; form: 0 none, 1 ELL, 2 CSR)
+GRAPH_STATS = ("form", "entries", "longest_row", "csr_layer_launches", "csr_gather_launches")
+GRAPH_ELL, GRAPH_CSR = 1, 2
+ELL_MAX_IN_DEGREE = 7  # kernels.h ELLW - 1
 # smaml_adapt_phases order (api.cpp AdPhases)
 ADAPT_PHASES = ("reserve_ms", "cache_alloc_ms", "cache_fill_ms", "steps_ms")
 
@@ -208,6 +216,54 @@ def graph_ell(edge_index: np.ndarray, num_nodes: int):
     return cols, vals
 
 
+def _edge_weight(edge_weight, E):
+    if edge_weight is None:
+        return None
+    ew = np.ascontiguousarray(edge_weight, dtype=np.float32).reshape(-1)
+    if ew.size != E:
+        raise ValueError(f"edge_weight has {ew.size} entries for {E} edges")
+    return ew
+
+
+def graph_csr(edge_index: np.ndarray, num_nodes: int, edge_weight=None):
+    """(rowptr [N + 1], cols [nnz], vals [nnz]) of the normalised adjacency in its general form
+    (smaml_graph_csr: any in-degree, optional edge weights)."""
+    L = lib()
+    ei = np.ascontiguousarray(edge_index, dtype=np.int64)
+    E = ei.shape[1]
+    ew = _edge_weight(edge_weight, E)
+    cap = E + num_nodes
+    rowptr = np.zeros(num_nodes + 1, np.int32)
+    cols = np.zeros(cap, np.int32)
+    vals = np.zeros(cap, np.float32)
+    nnz = ctypes.c_int64()
+    check(L.smaml_graph_csr(ei.ctypes.data_as(PI64), ew.ctypes.data_as(PF32) if ew is not None else None, E, num_nodes,
+                            rowptr.ctypes.data_as(PI32), cols.ctypes.data_as(PI32), vals.ctypes.data_as(PF32), cap,
+                            ctypes.byref(nnz)))
+    return rowptr, cols[:nnz.value].copy(), vals[:nnz.value].copy()
+
+
+def set_graph_auto(ctx, edge_index, edge_weight=None, skip_same=False):
+    """Upload the graph to ``ctx`` in the form it needs: the ELL (``ctx.set_graph``) for an unweighted graph whose
+    in-degree is at most 7 -- the path every such graph has always taken --, the CSR form
+    (``ctx.set_graph_weighted``) for every other. ``skip_same``: do nothing if ``ctx.graph_key`` says that this
+    graph, in this form, is the live one. Returns True if it uploaded."""
+    ei = np.ascontiguousarray(edge_index, dtype=np.int64)
+    ew = _edge_weight(edge_weight, ei.shape[1])
+    ell = ew is None
+    if ell and ei.size and ei.min() >= 0:  # (an index out of range: left to set_graph's own message)
+        dst = ei[1][ei[0] != ei[1]]
+        ell = dst.size == 0 or int(np.bincount(dst).max()) <= ELL_MAX_IN_DEGREE
+    key = ei.tobytes() if ell else (b"csr", ei.tobytes(), None if ew is None else ew.tobytes())
+    if skip_same and ctx.graph_key == key:
+        return False
+    if ell:
+        ctx.set_graph(ei)
+    else:
+        ctx.set_graph_weighted(ei, ew)
+    return True
+
+
 def ptr(t) -> int:
     return t.data_ptr()
 
@@ -260,6 +316,23 @@ class Context:
         ei = np.ascontiguousarray(edge_index, dtype=np.int64)
         check(self._L.smaml_set_graph(self._h, ei.ctypes.data_as(PI64), ei.shape[1]))
         self.graph_key = ei.tobytes()
+
+    def set_graph_weighted(self, edge_index: np.ndarray, edge_weight=None):
+        """The graph in its general form (smaml_set_graph_weighted): any in-degree, ``edge_weight`` [E] or None."""
+        ei = np.ascontiguousarray(edge_index, dtype=np.int64)
+        ew = _edge_weight(edge_weight, ei.shape[1])
+        check(self._L.smaml_set_graph_weighted(self._h, ei.ctypes.data_as(PI64),
+                                               ew.ctypes.data_as(PF32) if ew is not None else None, ei.shape[1]))
+        self.graph_key = (b"csr", ei.tobytes(), None if ew is None else ew.tobytes())
+
+    def graph_stats(self):
+        """{counter: value} of the live graph (smaml_graph_stats; host counters, no sync)."""
+        n = len(GRAPH_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_graph_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(GRAPH_STATS)}
 
     def set_gcn_params(self, flat):
         self._gcn = flat

@@ -97,7 +97,7 @@ class AdaptResult:
 def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_name: str, epochs: int = 15,
           max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
           val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
-          dropout_seed: int = 0, orders=None, train_base: bool = False) -> AdaptResult:
+          dropout_seed: int = 0, orders=None, train_base: bool = False, edge_weight=None) -> AdaptResult:
     """``dropout`` = (STGCN dropout_rate, lstm_dropout) of the train-mode steps (the reference
     adapts in train mode: (0.2, 0.2)); validation runs without dropout (eval mode).
     ``orders``: optional per-epoch sample permutations of the training windows (default: drawn
@@ -106,11 +106,12 @@ def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_
     "for ALL parameters" announce and its ``no_grad`` withholds (F2): each epoch is one
     ``smaml_adapt_steps_full`` call, one Adam state and one joint gradient clip over both vectors, no
     per-window feature cache; ``AdaptResult.gcn`` is the adapted flat GCN vector and the validation runs on
-    the adapted base."""
+    the adapted base. ``edge_weight`` [E] (optional): the graph's edge weights, as PyG's ``GCNConv`` takes them."""
     dev = torch.device(device)
     ctx = ctx or _capi.Context(dims, dev.index or 0)
     ei = edge_index.detach().cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
-    ctx.set_graph(ei)
+    ew = edge_weight.detach().cpu().numpy() if torch.is_tensor(edge_weight) else edge_weight
+    _capi.set_graph_auto(ctx, ei, ew)  # the ELL, or the CSR form for a weighted graph or an in-degree above 7
     gflat = params.pack(gcn, dims, which=1, device=dev)
     ctx.set_gcn_params(gflat)
     th = params.pack(theta, dims, which=0, device=dev)
@@ -189,7 +190,7 @@ def check_orders(orders, n_trains, epochs: int) -> List[np.ndarray]:
 def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, region_names, epochs: int = 15,
                max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
                val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
-               dropout_seed: int = 0, orders=None) -> List[AdaptResult]:
+               dropout_seed: int = 0, orders=None, edge_weight=None) -> List[AdaptResult]:
     """``adapt`` for several regions at once (main.py adapts its regions one after another): every region
     starts from the same meta-trained ``theta`` and keeps its own stream, climate optimiser settings,
     ``ClimateAwareLRScheduler`` (stepped on its own epoch mean), shuffle orders and Adam state, and each
@@ -204,7 +205,8 @@ def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, reg
         raise ValueError(f"{len(region_names)} region names for {R} streams")
     ctx = ctx or _capi.Context(dims, dev.index or 0)
     ei = edge_index.detach().cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
-    ctx.set_graph(ei)
+    ew = edge_weight.detach().cpu().numpy() if torch.is_tensor(edge_weight) else edge_weight
+    _capi.set_graph_auto(ctx, ei, ew)  # the ELL, or the CSR form for a weighted graph or an in-degree above 7
     gflat = params.pack(gcn, dims, which=1, device=dev)
     ctx.set_gcn_params(gflat)
     th0 = params.pack(theta, dims, which=0, device=dev)

@@ -150,6 +150,99 @@ int build_ell(const int64_t* ei, int64_t E, int N, std::vector<int32_t>& cols, s
   return SMAML_OK;
 }
 
+// A_hat as CSR for any in-degree and optional edge weights (smaml.h: smaml_graph_csr states the rules; PyG 2.x
+// gcn_norm with edge_weight). Row t: its in-edges in input order, then its self loop; entries of value 0 dropped.
+// With ew == nullptr and in-degree <= 7 these are build_ell's non-padding entries, bit for bit.
+int build_csr(const int64_t* ei, const float* ew, int64_t E, int N, std::vector<int32_t>& rowptr,
+              std::vector<int32_t>& cols, std::vector<float>& vals) {
+  const int64_t* src = ei;
+  const int64_t* dst = ei + E;
+  for (int64_t e = 0; e < E; ++e) {
+    if (src[e] < 0 || src[e] >= N || dst[e] < 0 || dst[e] >= N)
+      return fail(SMAML_EINVAL, "edge " + std::to_string(e) + " (" + std::to_string(src[e]) + " -> " +
+                                    std::to_string(dst[e]) + ") references a node outside [0, num_nodes)");
+    if (ew && !(ew[e] >= 0.f && std::isfinite(ew[e])))
+      return fail(SMAML_EINVAL, "edge " + std::to_string(e) + " (" + std::to_string(src[e]) + " -> " +
+                                    std::to_string(dst[e]) + ") has a negative, NaN or infinite weight");
+  }
+  if (E + (int64_t)N > INT32_MAX) return fail(SMAML_EINVAL, "the graph has more than 2^31 - 1 entries");
+  std::vector<float> loop(N, 1.f);  // add_remaining_self_loops: the last input loop's weight, else 1
+  if (ew)
+    for (int64_t e = 0; e < E; ++e)
+      if (src[e] == dst[e]) loop[src[e]] = ew[e];
+  std::vector<double> deg(N);
+  for (int i = 0; i < N; ++i) deg[i] = loop[i];
+  for (int64_t e = 0; e < E; ++e)
+    if (src[e] != dst[e]) deg[dst[e]] += ew ? (double)ew[e] : 1.0;
+  std::vector<float> dinv(N);
+  for (int i = 0; i < N; ++i) {
+    const float d = (float)deg[i];
+    dinv[i] = d > 0.f ? 1.f / std::sqrt(d) : 0.f;
+  }
+  auto value = [&](int64_t s, float w, int64_t t) { return (dinv[s] * w) * dinv[t]; };
+  rowptr.assign((size_t)N + 1, 0);
+  for (int64_t e = 0; e < E; ++e)
+    if (src[e] != dst[e] && value(src[e], ew ? ew[e] : 1.f, dst[e]) != 0.f) ++rowptr[dst[e] + 1];
+  for (int i = 0; i < N; ++i) {
+    if (value(i, loop[i], i) != 0.f) ++rowptr[i + 1];
+    rowptr[i + 1] += rowptr[i];
+  }
+  cols.assign((size_t)rowptr[N], 0);
+  vals.assign((size_t)rowptr[N], 0.f);
+  std::vector<int32_t> pos(rowptr.begin(), rowptr.end() - 1);
+  for (int64_t e = 0; e < E; ++e) {
+    const int64_t s = src[e], t = dst[e];
+    if (s == t) continue;
+    const float v = value(s, ew ? ew[e] : 1.f, t);
+    if (v == 0.f) continue;
+    cols[pos[t]] = (int32_t)s;
+    vals[pos[t]++] = v;
+  }
+  for (int i = 0; i < N; ++i) {
+    const float v = value(i, loop[i], i);
+    if (v == 0.f) continue;
+    cols[pos[i]] = i;
+    vals[pos[i]++] = v;
+  }
+  return SMAML_OK;
+}
+
+// The ELL's non-zero entries as CSR, in the ELL's order (what the transpose and the graph's counters walk).
+void ell_to_csr(int N, const std::vector<int32_t>& ec, const std::vector<float>& ev, std::vector<int32_t>& rowptr,
+                std::vector<int32_t>& cols, std::vector<float>& vals) {
+  rowptr.assign((size_t)N + 1, 0);
+  cols.clear();
+  vals.clear();
+  for (int t = 0; t < N; ++t) {
+    for (int e = 0; e < ELLW; ++e)
+      if (ev[(size_t)t * ELLW + e] != 0.f) {
+        cols.push_back(ec[(size_t)t * ELLW + e]);
+        vals.push_back(ev[(size_t)t * ELLW + e]);
+      }
+    rowptr[t + 1] = (int32_t)cols.size();
+  }
+}
+
+// A_hat^T as CSR from A_hat's CSR: entry (t, e) (row t gathers column cols[e] with weight vals[e]) becomes an
+// entry of row cols[e] of the transpose, in ascending t and, within t, in stored order (fixed order)
+void csr_transpose(int N, const std::vector<int32_t>& rowptr, const std::vector<int32_t>& cols,
+                   const std::vector<float>& vals, std::vector<int32_t>& tp, std::vector<int32_t>& tc,
+                   std::vector<float>& tv) {
+  tp.assign((size_t)N + 1, 0);
+  for (int32_t j : cols) ++tp[j + 1];
+  for (int i = 0; i < N; ++i) tp[i + 1] += tp[i];
+  tc.resize(tp[N]);
+  tv.resize(tp[N]);
+  std::vector<int32_t> pos(tp.begin(), tp.end() - 1);
+  for (int t = 0; t < N; ++t)
+    for (int32_t e = rowptr[t]; e < rowptr[t + 1]; ++e) {
+      const int j = cols[e];
+      tc[pos[j]] = t;
+      tv[pos[j]] = vals[e];
+      ++pos[j];
+    }
+}
+
 // one kernel per timing category (bench roofline = one kernel's launches)
 // (the *_WALL categories: the wall time of a sweep whose diagonals ran as concurrent row chunks on side
 // streams -- events on the caller's stream around the fork / join -- beside the per-chunk kernel times)
@@ -267,6 +360,12 @@ struct smaml_ctx {
   // The graph, all five set or none (smaml_set_graph): the normalised ELL (int32 columns, float values)
   // and A_hat^T as CSR (GCNConv backward's aggregation of the t = 0 rows)
   HipBuf ell_c, ell_v, tr_p, tr_c, tr_v;
+  // The other form (smaml_set_graph_weighted): A_hat as CSR with its edge weights folded in, no degree limit.
+  // graph_form says which of the two the entry points read (tr_* belongs to it); the other's buffers stay
+  // allocated. graph_stats: smaml_graph_stats [1] .. [4].
+  HipBuf csr_p, csr_c, csr_v;
+  int graph_form = 0;  // 0 none, 1 ELL, 2 CSR
+  int64_t graph_stats[5] = {};
   HipBuf bw_scratch;  // GCNConv backward: [rows][max(cin, cout)] x 2 floats
   // smaml_backward_base: conv1..conv3's recomputed activations [3][R][Hc], two gradient buffers
   // [2][R][max(Hc, Cin0)] and the samples' inputs in one piece [R][Cin0], R = nsamples*T*N (grows only)
@@ -404,6 +503,22 @@ struct smaml_ctx {
 };
 
 namespace {
+
+// The live graph as the launchers take it (kernels.h GraphView): the form and the tables of A_hat and A_hat^T.
+GraphView graph_view(smaml_ctx* c) {
+  GraphView g;
+  g.form = c->graph_form;
+  g.ell_c = c->ell_c.as<int32_t>();
+  g.ell_v = c->ell_v.as<float>();
+  g.csr_p = c->csr_p.as<int32_t>();
+  g.csr_c = c->csr_c.as<int32_t>();
+  g.csr_v = c->csr_v.as<float>();
+  g.tr_p = c->tr_p.as<int32_t>();
+  g.tr_c = c->tr_c.as<int32_t>();
+  g.tr_v = c->tr_v.as<float>();
+  g.csr_launches = &c->graph_stats[3];
+  return g;
+}
 
 int ensure_device(smaml_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
@@ -824,8 +939,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
   const int zb = w.Z * w.B;
   const float* src = nullptr;
   float* bufs[2] = {w.gcnA, w.gcnB};
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
+  const GraphView gv = graph_view(c);
   if (gcn_mlp_supported(d) && c->kn.gcn_fused) {
     HIP_TRY(c->gcn_wimg.grow(gcn_wimg_bytes(d)));
     char* wimg = c->gcn_wimg.as<char>();
@@ -846,7 +960,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
       float* dst = last ? w.F : bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv,
                              d.N, d.N, &w.drop, rps));
       src = dst;
     }
@@ -860,7 +974,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
       float* dst = bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * w.Z * rpsC * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, w.Z, 1, k == 0 ? first_tab : nullptr, src, dst, false, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv,
                              rpsC, 0, nullptr));
       src = dst;
     }
@@ -871,7 +985,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
       float* dst = last ? w.F : bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
+                             c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv,
                              d.N, d.N, &w.drop, rps));
       src = dst;
     }
@@ -883,7 +997,7 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
     float* dst = last ? w.F : bufs[k & 1];
     TIMED(c, s, C_GCN, 2.0 * zb * rps * c->go.cin[k] * d.Hc,
           launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, src, dst, last, true,
-                           c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v,
+                           c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv,
                            rps, d.N, &w.drop));
     src = dst;
   }
@@ -904,8 +1018,7 @@ int run_gcn_keep(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, floa
   w.fcompact = 0;
   const int rps = d.T * d.N;
   const int zb = w.Z * w.B;
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
+  const GraphView gv = graph_view(c);
   if (gcn_mlp_supported(d) && c->kn.gcn_fused) {
     char* wimg = c->gcn_wimg.as<char>();  // (grown by the caller before its first launch)
     GcnWOff wo;
@@ -922,7 +1035,7 @@ int run_gcn_keep(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, floa
       TIMED(c, s, C_GCN, 2.0 * zb * d.N * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, k == 0 ? nullptr : h[k - 1],
                              last ? w.F : h[k], last, true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k],
-                             d.Hc, ell_c, ell_v, d.N, d.N, &w.drop, rps, rps, rps));
+                             d.Hc, gv, d.N, d.N, &w.drop, rps, rps, rps));
     }
     HIP_TRY(hipGetLastError());
     return SMAML_OK;
@@ -932,7 +1045,7 @@ int run_gcn_keep(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, floa
     TIMED(c, s, C_GCN, 2.0 * zb * rps * c->go.cin[k] * d.Hc,
           launch_gcn_layer(s, d, k, zb, w.B, k == 0 ? xtab_dev : nullptr, k == 0 ? nullptr : h[k - 1],
                            last ? w.F : h[k], last, true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k],
-                           d.Hc, ell_c, ell_v, rps, d.N, &w.drop));
+                           d.Hc, gv, rps, d.N, &w.drop));
     stats[2] += 1;
   }
   HIP_TRY(hipGetLastError());
@@ -1499,8 +1612,7 @@ int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
       // with the graph), then the kind-1 mask of (step e, layer k) at the batch-wide element index
       // ((done + b) T N + row) Hc + channel = base + the buffer's own linear index
       const int rps = d.T * d.N;
-      const int32_t* ell_c = c->ell_c.as<int32_t>();
-      const float* ell_v = c->ell_v.as<float>();
+      const GraphView gv = graph_view(c);
       float* bufs[2] = {cw.gcnA, cw.gcnB};
       for (int z = 0; z < g; ++z) {
         const float* src = nullptr;
@@ -1509,7 +1621,7 @@ int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
           float* dst = last ? cw.F + (int64_t)z * fslab : bufs[k & 1];
           TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
                 launch_gcn_layer(s, d, k, B, B, k == 0 ? xt : nullptr, src, dst, last, true, c->gcn + c->go.w[k],
-                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N, nullptr));
+                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N, nullptr));
           if (!last)
             TIMED(c, s, C_GCN, 0,
                   launch_ens_dropout(s, dst, (int64_t)B * rps * d.Hc, 1, a.seed, 1, e0 + z, k, thr_gcn,
@@ -1554,7 +1666,7 @@ int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
   return SMAML_OK;
 }
 
-bool graph_set(const smaml_ctx* c) { return c->ell_c.ptr && c->ell_v.ptr; }
+bool graph_set(const smaml_ctx* c) { return c->graph_form != 0; }
 
 int require_ready(smaml_ctx* c) {
   if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
@@ -1620,8 +1732,14 @@ int gcn_conv_bwd(smaml_ctx* c, hipStream_t s, const float* x, int rows, int rps,
     // dW = dz^T (A_hat x), db = sum_rows dz: the split-K weight-gradient GEMM with its bias column
     const float* ax = x;
     if (ng > 0) {
-      launch_gather_rows(s, x, t0, rows, cin, ng, c->ell_c.as<int32_t>(), c->ell_v.as<float>(), nullptr, nullptr,
-                         nullptr, rps);
+      // A_hat x through the ELL, or through A_hat's CSR (k_gather_rows's CSR sum, the one A_hat^T takes below)
+      const GraphView gv = graph_view(c);
+      if (gv.form == 2) {
+        launch_gather_rows(s, x, t0, rows, cin, ng, nullptr, nullptr, gv.csr_p, gv.csr_c, gv.csr_v, rps);
+        ++c->graph_stats[4];
+      } else {
+        launch_gather_rows(s, x, t0, rows, cin, ng, gv.ell_c, gv.ell_v, nullptr, nullptr, nullptr, rps);
+      }
       ax = t0;
     }
     Work w = c->w;
@@ -1637,6 +1755,7 @@ int gcn_conv_bwd(smaml_ctx* c, hipStream_t s, const float* x, int rows, int rps,
       launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, t1);
       launch_gather_rows(s, t1, dx, rows, cin, ng, nullptr, nullptr, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
                          c->tr_v.as<float>(), rps);
+      if (c->graph_form == 2) ++c->graph_stats[4];
     } else {
       launch_gemm_nn_plain(s, dz, rows, cout, weight, cin, dx);
     }
@@ -1667,6 +1786,7 @@ int gcn_backward_chain(smaml_ctx* c, hipStream_t s, const float* x0, float* cons
             launch_gcn_dz(s, g, rows, d.Hc, W, cin, h[l - 1], sc, rps, d.N, c->tr_p.as<int32_t>(), c->tr_c.as<int32_t>(),
                           c->tr_v.as<float>(), dz_top, gn));
       if (stats) stats[3] += 1;
+      if (c->graph_form == 2) ++c->graph_stats[4];
     } else {
       TIMED(c, s, cat, 2.0 * rows * d.Hc * cin, {
         TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, d.N, gn, nullptr, 0, 0));
@@ -1795,6 +1915,25 @@ int smaml_destroy(smaml_ctx* c) {
   return SMAML_OK;
 }
 
+// Upload A_hat^T (both forms' backward aggregation) and record the graph's counters; the caller has uploaded
+// A_hat's own table. Everything that can fail on the host has happened before the first of these calls.
+static int upload_transpose(smaml_ctx* c, int form, const std::vector<int32_t>& rowptr, const std::vector<int32_t>& tp,
+                            const std::vector<int32_t>& tc, const std::vector<float>& tv) {
+  HIP_TRY(hipMemcpy(c->tr_p.ptr, tp.data(), tp.size() * 4, hipMemcpyHostToDevice));
+  if (!tc.empty()) {
+    HIP_TRY(hipMemcpy(c->tr_c.ptr, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->tr_v.ptr, tv.data(), tv.size() * 4, hipMemcpyHostToDevice));
+  }
+  int32_t longest = 0;
+  for (size_t t = 0; t + 1 < rowptr.size(); ++t) longest = std::max(longest, rowptr[t + 1] - rowptr[t]);
+  c->graph_form = form;
+  c->graph_stats[0] = form;
+  c->graph_stats[1] = rowptr.back();
+  c->graph_stats[2] = longest;
+  c->graph_stats[3] = c->graph_stats[4] = 0;
+  return SMAML_OK;
+}
+
 int smaml_set_graph(smaml_ctx* c, const int64_t* edge_index_host, int64_t num_edges) {
   if (!c || !edge_index_host) return fail(SMAML_EINVAL, "NULL argument");
   TRY(ensure_device(c));
@@ -1802,38 +1941,67 @@ int smaml_set_graph(smaml_ctx* c, const int64_t* edge_index_host, int64_t num_ed
   std::vector<float> vals;
   TRY(build_ell(edge_index_host, num_edges, c->d.N, cols, vals));
   ad_cache_invalidate(c);
-  // A_hat^T as CSR: entry (t, e) of the ELL (row t gathers column cols[t][e] with weight vals[t][e])
-  // becomes row cols[t][e] of the transpose, in ascending t (fixed order)
   const int N = c->d.N;
-  std::vector<int32_t> tp(N + 1, 0), tc;
-  std::vector<float> tv;
-  for (int t = 0; t < N; ++t)
-    for (int e = 0; e < ELLW; ++e)
-      if (vals[(size_t)t * ELLW + e] != 0.f) ++tp[cols[(size_t)t * ELLW + e] + 1];
-  for (int i = 0; i < N; ++i) tp[i + 1] += tp[i];
-  tc.resize(tp[N]);
-  tv.resize(tp[N]);
-  std::vector<int32_t> pos(tp.begin(), tp.end() - 1);
-  for (int t = 0; t < N; ++t)
-    for (int e = 0; e < ELLW; ++e) {
-      const float v = vals[(size_t)t * ELLW + e];
-      if (v == 0.f) continue;
-      const int j = cols[(size_t)t * ELLW + e];
-      tc[pos[j]] = t;
-      tv[pos[j]] = v;
-      ++pos[j];
-    }
+  std::vector<int32_t> rp, rc, tp, tc;
+  std::vector<float> rv, tv;
+  ell_to_csr(N, cols, vals, rp, rc, rv);
+  csr_transpose(N, rp, rc, rv, tp, tc, tv);
   const int64_t ell = (int64_t)cols.size() * 4, nnz = std::max<int64_t>((int64_t)tc.size(), 1) * 4;
   HIP_TRY(grow_all<HipAlloc>(
       {{&c->ell_c, ell}, {&c->ell_v, ell}, {&c->tr_p, (int64_t)tp.size() * 4}, {&c->tr_c, nnz}, {&c->tr_v, nnz}}));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(c->ell_c.ptr, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->ell_v.ptr, vals.data(), vals.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->tr_p.ptr, tp.data(), tp.size() * 4, hipMemcpyHostToDevice));
-  if (!tc.empty()) {
-    HIP_TRY(hipMemcpy(c->tr_c.ptr, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->tr_v.ptr, tv.data(), tv.size() * 4, hipMemcpyHostToDevice));
+  return upload_transpose(c, 1, rp, tp, tc, tv);
+}
+
+int smaml_graph_csr(const int64_t* edge_index_host, const float* edge_weight_host, int64_t num_edges, int32_t num_nodes,
+                    int32_t* rowptr_host, int32_t* cols_host, float* vals_host, int64_t cap, int64_t* nnz_out) {
+  if (nnz_out) *nnz_out = 0;
+  if (!edge_index_host || !rowptr_host || !nnz_out || num_nodes <= 0 || num_edges < 0 || cap < 0 ||
+      (cap > 0 && (!cols_host || !vals_host)))
+    return fail(SMAML_EINVAL, "bad arguments to smaml_graph_csr");
+  std::vector<int32_t> rp, cols;
+  std::vector<float> vals;
+  TRY(build_csr(edge_index_host, edge_weight_host, num_edges, num_nodes, rp, cols, vals));
+  *nnz_out = (int64_t)cols.size();
+  if ((int64_t)cols.size() > cap)
+    return fail(SMAML_EINVAL, "smaml_graph_csr: cap (" + std::to_string(cap) + ") is below the graph's " +
+                                  std::to_string(cols.size()) + " entries");
+  std::memcpy(rowptr_host, rp.data(), rp.size() * 4);
+  if (!cols.empty()) {
+    std::memcpy(cols_host, cols.data(), cols.size() * 4);
+    std::memcpy(vals_host, vals.data(), vals.size() * 4);
   }
+  return SMAML_OK;
+}
+
+int smaml_set_graph_weighted(smaml_ctx* c, const int64_t* edge_index_host, const float* edge_weight_host,
+                             int64_t num_edges) {
+  if (!c || !edge_index_host || num_edges < 0) return fail(SMAML_EINVAL, "bad arguments to smaml_set_graph_weighted");
+  TRY(ensure_device(c));
+  const int N = c->d.N;
+  std::vector<int32_t> rp, rc, tp, tc;
+  std::vector<float> rv, tv;
+  TRY(build_csr(edge_index_host, edge_weight_host, num_edges, N, rp, rc, rv));
+  ad_cache_invalidate(c);
+  csr_transpose(N, rp, rc, rv, tp, tc, tv);
+  const int64_t nnz = std::max<int64_t>((int64_t)rc.size(), 1) * 4, np = (int64_t)rp.size() * 4;
+  HIP_TRY(grow_all<HipAlloc>(
+      {{&c->csr_p, np}, {&c->csr_c, nnz}, {&c->csr_v, nnz}, {&c->tr_p, np}, {&c->tr_c, nnz}, {&c->tr_v, nnz}}));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(c->csr_p.ptr, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
+  if (!rc.empty()) {
+    HIP_TRY(hipMemcpy(c->csr_c.ptr, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->csr_v.ptr, rv.data(), rv.size() * 4, hipMemcpyHostToDevice));
+  }
+  return upload_transpose(c, 2, rp, tp, tc, tv);
+}
+
+int smaml_graph_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad graph_stats arguments");
+  for (int i = 0; i < 5 && i < cap; ++i) counts[i] = c->graph_stats[i];
+  if (count) *count = 5;
   return SMAML_OK;
 }
 
@@ -1893,7 +2061,7 @@ int smaml_gcn_conv(smaml_ctx* c, void* stream, const float* x, int32_t rows, int
   TRY(ensure_device(c));
   hipStream_t s = (hipStream_t)stream;
   launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, false, weight, bias, cin, cout,
-                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, c->d.N);
+                   graph_view(c), rows, c->d.N);
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1912,7 +2080,7 @@ int smaml_gcn_conv_ex(smaml_ctx* c, void* stream, const float* x, int32_t rows, 
   TRY(check_device_error(c));
   hipStream_t s = (hipStream_t)stream;
   launch_gcn_layer(s, c->d, 0, 1, 1, nullptr, x, out, false, relu, weight, bias, cin, cout,
-                   c->ell_c.as<int32_t>(), c->ell_v.as<float>(), rows, plain ? 0 : c->d.N);
+                   graph_view(c), rows, plain ? 0 : c->d.N);
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -2098,8 +2266,7 @@ int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan
   const bool img = cw.gimg.th && cw.gimg_src == theta;
   const char* gimg = img ? cw.gimg.th : nullptr;
   const int64_t gimg_off = cw.gimg.off[0][0];
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
+  const GraphView gv = graph_view(c);
   const int cin0 = c->po.lay[0].cin;
   GcnWOff wo;
   for (int k = 0; k < 4; ++k) {
@@ -2148,7 +2315,7 @@ int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan
           float* dst = last ? Frun : bufs[k & 1];
           TIMED(c, s, C_GCN, 2.0 * B * nrun * d.N * c->go.cin[k] * d.Hc,
                 launch_gcn_layer(s, d, k, B, B, k == 0 ? rtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
-                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, nrun * d.N, 0, nullptr));
+                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, nrun * d.N, 0, nullptr));
           from = dst;
         }
       }
@@ -2169,7 +2336,7 @@ int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan
       float* dst = last ? F0 : bufs[k & 1];
       TIMED(c, s, C_GCN, 2.0 * M * c->go.cin[k] * d.Hc,
             launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
-                             c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, d.N, d.N, nullptr, d.T * d.N));
+                             c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, d.N, d.N, nullptr, d.T * d.N));
       from = dst;
     }
     TIMED(c, s, C_XG, 2.0 * slot * cin0, launch_xg_rows(s, d, cw, F0, M, theta, c->po, gimg, gimg_off, xg0));
@@ -2350,8 +2517,7 @@ int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p
   const bool img = cw.gimg.th && cw.gimg_src == theta;
   const char* gimg = img ? cw.gimg.th : nullptr;
   const int64_t gimg_off = cw.gimg.off[0][0];
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
+  const GraphView gv = graph_view(c);
   const int cin0 = c->po.lay[0].cin;
   GcnWOff wo;
   for (int k = 0; k < 4; ++k) {
@@ -2374,7 +2540,7 @@ int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p
         float* to = last ? dst + (int64_t)s0 * d.N * d.Hc : bufs[k & 1];
         TIMED(c, s, C_GCN, 2.0 * n * rps * c->go.cin[k] * d.Hc,
               launch_gcn_layer(s, d, k, n, ns, k == 0 ? tab + s0 : nullptr, from, to, last, true, c->gcn + c->go.w[k],
-                               c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, ell_rows, nullptr,
+                               c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, ell_rows, nullptr,
                                d.T * d.N));
         from = to;
       }
@@ -2464,7 +2630,7 @@ int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p
             float* to = last ? Frun + (int64_t)z * fslab : bufs[k & 1];
             TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
                   launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab + (int64_t)z * B : nullptr, from, to, last, true,
-                                   c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N,
+                                   c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N,
                                    nullptr));
             if (!last)
               TIMED(c, s, C_GCN, 0,
@@ -3179,8 +3345,7 @@ static int adapt_run(smaml_ctx* c, hipStream_t s, const AdaptCall& a) {
           for (int l = 0; l < 3; ++l) {
             TIMED(c, s, C_GCN, 2.0 * rows * c->go.cin[l] * d.Hc,
                   launch_gcn_layer(s, d, l, B, B, l == 0 ? xt : nullptr, l == 0 ? nullptr : f.h[l - 1], f.h[l], false, true,
-                                   c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, c->ell_c.as<int32_t>(),
-                                   c->ell_v.as<float>(), d.T * d.N, d.N, &w.drop));
+                                   c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, graph_view(c), d.T * d.N, d.N, &w.drop));
             c->af_stats[5] += 1;
           }
         }
@@ -3525,12 +3690,11 @@ int smaml_backward_base(smaml_ctx* c, void* stream, const float* theta, const fl
   TRY(upload_xtab(c, s, x_host, nsamples));
   const float* const* xt = nullptr;
   TRY(xtab_at(c, 0, &xt));
-  const int32_t* ell_c = c->ell_c.as<int32_t>();
-  const float* ell_v = c->ell_v.as<float>();
+  const GraphView gv = graph_view(c);
   for (int k = 0; k < 3; ++k)
     TIMED(c, s, C_GCN, 2.0 * R * c->go.cin[k] * d.Hc,
           launch_gcn_layer(s, d, k, nsamples, nsamples, k == 0 ? xt : nullptr, k == 0 ? nullptr : h[k - 1], h[k], false,
-                           true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, ell_c, ell_v, rps, d.N,
+                           true, c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N,
                            &w.drop));
   // dZ4 = dF through conv4's ReLU, per sample: layer 0's dG slab (left by the BPTT) times W_ih0
   const float* Wih0 = theta + c->po.lay[0].wih;

@@ -385,12 +385,28 @@ double fwd_wave(const Dims& d, const Work& w, const ParamOff& po, int diag, int 
 
 const char* products_info();  // product form per GEMM family as built (kernels.hip)
 
+// The graph a GCN launch gathers through: the ELL of A_hat (width ELLW, smaml_set_graph) or its CSR
+// (any in-degree, optional edge weights: smaml_set_graph_weighted), and A_hat^T as CSR in either form.
+// csr_launches (optional): += 1 per k_gcn_layer launch whose gather reads the CSR (smaml_graph_stats [3]).
+struct GraphView {
+  int form = 0;  // 0 none, 1 ELL, 2 CSR
+  const int* ell_c = nullptr;
+  const float* ell_v = nullptr;
+  const int* csr_p = nullptr;  // A_hat, form 2: [N + 1], entries in input order, self loop last
+  const int* csr_c = nullptr;
+  const float* csr_v = nullptr;
+  const int* tr_p = nullptr;  // A_hat^T, both forms
+  const int* tr_c = nullptr;
+  const float* tr_v = nullptr;
+  int64_t* csr_launches = nullptr;
+};
+
 // ---- launchers (kernels.hip) ----
 // drop_rps: rows per sample of the dropout element index (default rows_per_sample; the t = 0 path of
 // run_gcn runs N-row "samples" but indexes masks as the T*N-row samples they belong to)
 void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, const float* const* xtab,
                       const float* src, float* dst, bool remap_lstm, bool relu, const float* W,
-                      const float* b, int cin, int cout, const int* ell_c, const float* ell_v, int rows_per_sample,
+                      const float* b, int cin, int cout, const GraphView& gv, int rows_per_sample,
                       int ell_rows, const Drop* drop = nullptr, int drop_rps = 0, int src_rps = 0, int dst_rps = 0);
 
 // Exact unsigned division by a run-time invariant d for n < 2^31 (one 64-bit multiply):

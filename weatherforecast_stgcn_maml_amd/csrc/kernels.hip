@@ -99,6 +99,31 @@ struct GcnA {
   }
 };
 
+// GcnA with the CSR of A_hat in place of the ELL (smaml_set_graph_weighted: any in-degree, edge weights): row q
+// sums its entries rp[q] .. rp[q + 1] in stored order with GcnA's fma4, so on a graph both forms accept the two
+// give the same bits (the CSR holds the ELL's non-zero entries in the ELL's order). One lane walks the whole row.
+struct GcnCsrA {
+  const float* const* tab;
+  const float* buf;
+  int64_t sstride;
+  const int* rp;
+  const int* rc;
+  const float* rv;
+  FastDiv rps_div;
+  int rps, ell_rows, cin, R;
+  __device__ __forceinline__ float4 operator()(int r, int k) const {
+    if (r >= R || k >= cin) return f4zero();
+    const int g = (int)rps_div.div((uint32_t)r), q = r - g * rps;
+    const float* base = tab ? tab[g] : buf + (int64_t)g * sstride;
+    if (q < ell_rows) {
+      float4 s = f4zero();
+      for (int e = rp[q], e1 = rp[q + 1]; e < e1; ++e) s = fma4(rv[e], ld4(base + (int64_t)rc[e] * cin + k), s);
+      return s;
+    }
+    return ld4(base + (int64_t)q * cin + k);
+  }
+};
+
 // Rows with no neighbours (t >= 1, F3): layer 1 reads the sample's window, layers 2-4 the
 // previous layer's [g][rps][cin] buffer, which is simply row-major [R][cin].
 struct GcnPlain {
@@ -118,7 +143,8 @@ struct GcnPlain {
 // so each input row is read once.
 using CfgGcn = GemmCfg<128, 256, 2, 4, true, true, SMAML_GCN_BK, SMAML_X6_GCN>;
 
-__global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(GcnA la, RowMajorKC lb, const float* __restrict__ bias,
+template <class LA>  // GcnA (ELL) or GcnCsrA: the gather of the t = 0 rows; everything else is shared
+__global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(LA la, RowMajorKC lb, const float* __restrict__ bias,
                                                            float* __restrict__ out, int cout, int remap, int relu,
                                                            int T, int N, int B, FastDiv ndiv, FastDiv bdiv, Drop dr,
                                                            uint32_t dsite, int drps, int orps) {
@@ -183,8 +209,8 @@ __global__ __launch_bounds__(CfgGcn::NTH) void k_gcn_layer(GcnA la, RowMajorKC l
 
 void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, const float* const* xtab,
                       const float* src, float* dst, bool remap_lstm, bool relu, const float* W,
-                      const float* b, int cin, int cout, const int* ell_c, const float* ell_v,
-                      int rows_per_sample, int ell_rows, const Drop* drop, int drop_rps, int src_rps, int dst_rps) {
+                      const float* b, int cin, int cout, const GraphView& gv, int rows_per_sample,
+                      int ell_rows, const Drop* drop, int drop_rps, int src_rps, int dst_rps) {
   // train-mode dropout after the ReLU of conv1..conv3 (hybrid_model.py:67,70,73)
   Drop dr{};
   uint32_t dsite = 0;
@@ -192,25 +218,25 @@ void launch_gcn_layer(hipStream_t s, const Dims& d, int layer, int Zb, int B, co
     dr = *drop;
     dsite = drop_site(dr.seed, 1, dr.step, layer);
   }
-  GcnA la;
-  la.tab = xtab;
-  la.buf = src;
   // src_rps / dst_rps > 0: sample g's rows_per_sample rows start at row g * src_rps of src (layers 2-4) and at
   // row g * dst_rps of dst (no remap): the t = 0 blocks of T*N-row samples (smaml_adapt_steps_full)
-  la.sstride = (int64_t)(src_rps > 0 ? src_rps : rows_per_sample) * cin;
-  la.ec = ell_c;
-  la.ev = ell_v;
-  la.rps_div = FastDiv((uint32_t)rows_per_sample);
-  la.rps = rows_per_sample;
-  la.ell_rows = ell_rows;
-  la.cin = cin;
-  la.R = Zb * rows_per_sample;
+  const int64_t sstride = (int64_t)(src_rps > 0 ? src_rps : rows_per_sample) * cin;
+  const FastDiv rps_div((uint32_t)rows_per_sample);
+  const int R = Zb * rows_per_sample;
   RowMajorKC lb{W, cout, cin};
-  dim3 grid((la.R + CfgGcn::BM - 1) / CfgGcn::BM, (cout + CfgGcn::BN - 1) / CfgGcn::BN);
-  k_gcn_layer<<<grid, CfgGcn::NTH, 0, s>>>(la, lb, b, dst, cout, remap_lstm ? 1 : 0, relu ? 1 : 0, d.T, d.N, B,
-                                           FastDiv((uint32_t)d.N), FastDiv((uint32_t)B), dr, dsite,
-                                           drop_rps > 0 ? drop_rps : rows_per_sample,
-                                           dst_rps > 0 ? dst_rps : rows_per_sample);
+  dim3 grid((R + CfgGcn::BM - 1) / CfgGcn::BM, (cout + CfgGcn::BN - 1) / CfgGcn::BN);
+  const FastDiv ndiv((uint32_t)d.N), bdiv((uint32_t)B);
+  const int drps = drop_rps > 0 ? drop_rps : rows_per_sample, orps = dst_rps > 0 ? dst_rps : rows_per_sample;
+  if (gv.form == 2 && ell_rows > 0) {
+    const GcnCsrA la{xtab, src, sstride, gv.csr_p, gv.csr_c, gv.csr_v, rps_div, rows_per_sample, ell_rows, cin, R};
+    k_gcn_layer<<<grid, CfgGcn::NTH, 0, s>>>(la, lb, b, dst, cout, remap_lstm ? 1 : 0, relu ? 1 : 0, d.T, d.N, B, ndiv,
+                                             bdiv, dr, dsite, drps, orps);
+    if (gv.csr_launches) ++*gv.csr_launches;
+  } else {
+    const GcnA la{xtab, src, sstride, gv.ell_c, gv.ell_v, rps_div, rows_per_sample, ell_rows, cin, R};
+    k_gcn_layer<<<grid, CfgGcn::NTH, 0, s>>>(la, lb, b, dst, cout, remap_lstm ? 1 : 0, relu ? 1 : 0, d.T, d.N, B, ndiv,
+                                             bdiv, dr, dsite, drps, orps);
+  }
 }
 
 // ====================================================================================

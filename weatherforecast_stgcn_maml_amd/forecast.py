@@ -90,7 +90,8 @@ def _stats(stats, C):
 
 
 def forecast(model, features, edge_index, stats=None, windows=None, batch: int = 64, score: bool = True,
-             return_pred: bool = True, ctx=None) -> ForecastResult:
+             return_pred: bool = True, ctx=None,
+             edge_weight=None) -> ForecastResult:
     """``model``: the drop-in ``HybridSTGCN_LSTM`` (its weights, prepared as ``evaluate_regional``
     prepares it); ``features``: the region's normalised ``[T_total, N, 24]`` stream (a tensor on the HIP
     device or a numpy array); ``stats``: ``{"mean": [..], "std": [..]}`` of the adaptation checkpoint
@@ -115,11 +116,14 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
     Hf, C = model.forecast_horizon, model.out_channels
     t_total, N = int(f.shape[0]), int(f.shape[1])
     ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
+    if ew is not None and not torch.is_tensor(ew):
+        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
     if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
     else:
         dims = model.dims(N)
-        _set_graph(ctx, ei)
+        _set_graph(ctx, ei, ew)
         gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
         ctx.set_gcn_params(gflat)
         theta, _ = model._packed(0, model._trainable_params(), dims, dev)
@@ -260,7 +264,8 @@ class RolloutResult:
 
 
 def rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, gap="midpoint", batch: int = 32,
-            score: bool = True, ctx=None) -> RolloutResult:
+            score: bool = True, ctx=None,
+            edge_weight=None) -> RolloutResult:
     """Autoregressive forecast of ``cycles`` x ``(Hf + 1)`` steps from every origin (``smaml_forecast_rollout``):
     each cycle's prediction is fed back as the weather channels of the next window, the exogenous channels
     come from ``features`` (use ``extend_stream`` to forecast past the last observation, with ``score=False``).
@@ -285,16 +290,19 @@ def rollout(model, features, edge_index, stats=None, origins=None, cycles: int =
     s = Hf + 1
     t_total, N = int(f.shape[0]), int(f.shape[1])
     ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
+    if ew is not None and not torch.is_tensor(ew):
+        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
     o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
     is_gap = (np.arange(R * s) % s) == 0
     gname = "midpoint" if g else "persistence"
     if o.size == 0:
         return RolloutResult(None, is_gap, None, None, None, None, 0, o, R, gname)
     if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
     else:
         dims = model.dims(N)
-        _set_graph(ctx, ei)
+        _set_graph(ctx, ei, ew)
         gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
         ctx.set_gcn_params(gflat)
         theta, _ = model._packed(0, model._trainable_params(), dims, dev)
@@ -385,7 +393,8 @@ class EnsembleResult:
 
 def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16, p_gcn=None, p_lstm=None,
                       seed=None, windows=None, batch: int = 32, score: bool = True, return_members: bool = False,
-                      ctx=None) -> EnsembleResult:
+                      ctx=None,
+                      edge_weight=None) -> EnsembleResult:
     """MC-dropout ensemble of ``forecast``: ``members`` stochastic forwards per window, member ``e`` under the
     library's masks of ``(seed, step e)`` (what ``model.train()``'s forward under ``no_grad`` computes), in
     lockstep over the member axis. ``p_gcn`` / ``p_lstm`` default to the model's own dropout rates
@@ -419,14 +428,17 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
     Hf, C = model.forecast_horizon, model.out_channels
     t_total, N = int(f.shape[0]), int(f.shape[1])
     ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
+    if ew is not None and not torch.is_tensor(ew):
+        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
     w = default_windows(t_total, T, Hf, score) if windows is None else np.asarray(windows, np.int32).reshape(-1)
     if w.size == 0:
         return EnsembleResult(None, None, None, None, None, None, None, None, 0, E, w, seed, p_gcn, p_lstm)
     if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
     else:
         dims = model.dims(N)
-        _set_graph(ctx, ei)
+        _set_graph(ctx, ei, ew)
         gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
         ctx.set_gcn_params(gflat)
         theta, _ = model._packed(0, model._trainable_params(), dims, dev)
@@ -524,7 +536,8 @@ class EnsembleRolloutResult:
 
 def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, members: int = 16,
                      p_gcn=None, p_lstm=None, seed=None, gap="midpoint", batch: int = 32, score: bool = True,
-                     return_members: bool = False, ctx=None) -> EnsembleRolloutResult:
+                     return_members: bool = False, ctx=None,
+                     edge_weight=None) -> EnsembleRolloutResult:
     """``rollout`` for an MC-dropout ensemble (``smaml_forecast_rollout_ensemble``): each of the ``members`` feeds
     its own forecast back in for ``cycles`` x ``(Hf + 1)`` steps, member ``e`` of cycle ``j`` under the library's
     masks of ``(seed, step 64 j + e)``. Defaults as ``ensemble_forecast`` (the model's own dropout rates,
@@ -557,6 +570,9 @@ def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycl
     s = Hf + 1
     t_total, N = int(f.shape[0]), int(f.shape[1])
     ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
+    if ew is not None and not torch.is_tensor(ew):
+        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
     o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
     is_gap = (np.arange(R * s) % s) == 0
     gname = "midpoint" if g else "persistence"
@@ -564,10 +580,10 @@ def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycl
     if o.size == 0:
         return EnsembleRolloutResult(None, None, None, is_gap, None, None, None, None, None, None, *tail)
     if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei)
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
     else:
         dims = model.dims(N)
-        _set_graph(ctx, ei)
+        _set_graph(ctx, ei, ew)
         gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
         ctx.set_gcn_params(gflat)
         theta, _ = model._packed(0, model._trainable_params(), dims, dev)

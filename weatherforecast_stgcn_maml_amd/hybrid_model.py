@@ -202,7 +202,7 @@ class HybridSTGCN_LSTM(nn.Module):
             return None
         return (p_gcn, p_lstm, draw_dropout_seed())
 
-    def _prepare(self, x, edge_index):
+    def _prepare(self, x, edge_index, edge_weight=None):
         if x.device.type != "cuda":
             raise _capi.SmamlError(-1, "HybridSTGCN_LSTM.forward runs on a HIP device only")
         T = self.base_stgcn.window_size
@@ -210,7 +210,7 @@ class HybridSTGCN_LSTM(nn.Module):
             raise ValueError(f"x has {x.shape[0]} rows, not a multiple of window_size={T}")
         dims = self.dims(x.shape[0] // T)
         ctx = _context(dims, x.device)
-        _set_graph(ctx, edge_index)
+        _set_graph(ctx, edge_index, edge_weight)
         gflat, fresh = self._packed(1, self._gcn_params(), dims, x.device)
         if fresh or getattr(ctx, "_gcn", None) is not gflat:  # another model may share the context
             ctx.set_gcn_params(gflat)
@@ -252,9 +252,9 @@ class HybridSTGCN_LSTM(nn.Module):
         self.__dict__.pop("_pack_cache", None)
 
     # ------------------------------------------------------------------ module API
-    def extract_base_features(self, x, edge_index):
-        """hybrid_model.py:60-78 -> [T*N, hidden_channels]."""
-        ctx, dims, theta = self._prepare(x, edge_index)
+    def extract_base_features(self, x, edge_index, edge_weight=None):
+        """hybrid_model.py:60-78 -> [T*N, hidden_channels] (``edge_weight`` as ``forward``)."""
+        ctx, dims, theta = self._prepare(x, edge_index, edge_weight)
         x = x.contiguous().float()
         pred = torch.empty(dims.num_nodes * dims.forecast_horizon, dims.output_channels, device=x.device)
         feats = torch.empty(x.shape[0], dims.hidden_channels, device=x.device)
@@ -266,9 +266,11 @@ class HybridSTGCN_LSTM(nn.Module):
         named += [("output_layer.weight", self.output_layer.weight), ("output_layer.bias", self.output_layer.bias)]
         return named
 
-    def forward(self, x, edge_index):
-        """hybrid_model.py:80-117 -> [N*forecast_horizon, out_channels] (rows n*Hf + h)."""
-        ctx, dims, theta = self._prepare(x, edge_index)
+    def forward(self, x, edge_index, edge_weight=None):
+        """hybrid_model.py:80-117 -> [N*forecast_horizon, out_channels] (rows n*Hf + h). ``edge_weight`` [E]
+        (optional): the weights PyG's ``GCNConv`` takes; a weighted graph, or an in-degree above 7, runs in the
+        library's CSR form, on the ``base_grad`` path too (no gradient flows to the weights)."""
+        ctx, dims, theta = self._prepare(x, edge_index, edge_weight)
         x = x.contiguous().float()
         named = self._trainable_params()
         drop = self._drop()

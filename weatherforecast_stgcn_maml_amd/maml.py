@@ -120,7 +120,7 @@ class MetaLearner:
 
     def __init__(self, dims: ModelDims, cfg: MamlConfig, gcn_params: dict, theta: dict,
                  edge_index: np.ndarray, device=None, process_group=None, task_group="auto",
-                 dropout=(0.0, 0.0), dropout_seed: int = 0, mem_share: float = 1.0):
+                 dropout=(0.0, 0.0), dropout_seed: int = 0, mem_share: float = 1.0, edge_weight=None):
         """``task_group``: tasks batched into one pass of the C driver. ``None`` = all of this
         rank's tasks at once; ``"auto"`` (default) = plan_task_group: second-order meta-steps run
         in groups small enough that every inner step's primal stays resident for the sweep.
@@ -142,7 +142,8 @@ class MetaLearner:
         self.dropout_seed = int(dropout_seed)
         self.device = torch.device(device or "cuda")
         self.ctx = _capi.Context(dims, self.device.index or 0)
-        self.ctx.set_graph(edge_index)
+        # the ELL, or the CSR form for a weighted graph (edge_weight [E]) or an in-degree above 7
+        _capi.set_graph_auto(self.ctx, edge_index, edge_weight)
         self.gcn = params.pack(gcn_params, dims, which=1, device=self.device)
         self.ctx.set_gcn_params(self.gcn)
         self.theta = params.pack(theta, dims, which=0, device=self.device)

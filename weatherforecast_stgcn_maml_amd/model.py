@@ -59,16 +59,30 @@ class _GraphMemo:
         self.value = value
         return value
 
+    def put_none(self, value):
+        """Remember that no tensor was passed (``edge_weight=None``) for ``value``."""
+        self.ref = None
+        self.version = -1
+        self.ptr = 0
+        self.value = value
 
-def _set_graph(ctx, edge_index: torch.Tensor):
+
+def _set_graph(ctx, edge_index: torch.Tensor, edge_weight=None):
+    """Make ``(edge_index, edge_weight)`` the context's graph, in the form it needs (``_capi.set_graph_auto``:
+    the ELL without weights and with in-degree <= 7, the CSR form otherwise). Both tensors are memoised."""
     memo = ctx.__dict__.setdefault("_ei_memo", _GraphMemo())
+    wmemo = ctx.__dict__.setdefault("_ew_memo", _GraphMemo())
     if memo.get(edge_index) is not None and ctx.graph_key is memo.value:
-        return
+        if (wmemo.ref is None if edge_weight is None else wmemo.get(edge_weight) is not None) and wmemo.value is memo.value:
+            return
     ei = edge_index.detach().to("cpu", torch.int64).contiguous().numpy()
-    key = ei.tobytes()
-    if ctx.graph_key != key:
-        ctx.set_graph(ei)
+    ew = None if edge_weight is None else edge_weight.detach().to("cpu", torch.float32).contiguous().numpy()
+    _capi.set_graph_auto(ctx, ei, ew, skip_same=True)
     memo.put(edge_index, ctx.graph_key)
+    if edge_weight is None:
+        wmemo.put_none(ctx.graph_key)
+    else:
+        wmemo.put(edge_weight, ctx.graph_key)
 
 
 class _Linear(nn.Module):
@@ -91,7 +105,9 @@ class GCNConv(nn.Module):
     runs ``smaml_gcn_conv``: rows < num_nodes of the graph aggregate over in-edges
     (symmetric normalisation), all other rows see only their self loop (F3). The graph has
     ``edge_index.max() + 1`` nodes; an ``x`` with fewer rows raises ``SmamlError`` (``SMAML_EINVAL``,
-    "rows must be at least num_nodes") where PyG raises an ``IndexError``."""
+    "rows must be at least num_nodes") where PyG raises an ``IndexError``. ``edge_weight`` [E] (optional) as in PyG's
+    ``forward(x, edge_index, edge_weight)``; a weighted graph, or one with an in-degree above 7, runs in the
+    library's CSR form (``smaml_set_graph_weighted``), every other in the ELL. No gradient flows to the weights."""
 
     def __init__(self, in_channels, out_channels, **kwargs):
         super().__init__()
@@ -100,7 +116,7 @@ class GCNConv(nn.Module):
         self.lin = _Linear(in_channels, out_channels)
         self.bias = nn.Parameter(torch.zeros(out_channels))
 
-    def graph_context(self, x, edge_index):
+    def graph_context(self, x, edge_index, edge_weight=None):
         """The library context this conv runs in for ``edge_index`` (graph uploaded once per tensor)."""
         memo = self.__dict__.setdefault("_ei_memo", _GraphMemo())
         n_graph = memo.get(edge_index)
@@ -111,11 +127,11 @@ class GCNConv(nn.Module):
                          hidden_channels=max(4, self.out_channels), lstm_hidden_size=32,
                          lstm_num_layers=1, forecast_horizon=1, output_channels=1)
         ctx = _context(dims, x.device)
-        _set_graph(ctx, edge_index)
+        _set_graph(ctx, edge_index, edge_weight)
         return ctx
 
-    def forward(self, x, edge_index):
-        ctx = self.graph_context(x, edge_index)
+    def forward(self, x, edge_index, edge_weight=None):
+        ctx = self.graph_context(x, edge_index, edge_weight)
         x = x.contiguous().float()
         if torch.is_grad_enabled() and (x.requires_grad or self.lin.weight.requires_grad or self.bias.requires_grad):
             return _GCNConvFn.apply(x, ctx, self.lin.weight, self.bias)
@@ -263,7 +279,7 @@ class STGCN(nn.Module):
             out += [conv.lin.weight, conv.bias]
         return out + [self.output_layer.weight, self.output_layer.bias]
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
         p = float(self.dropout.p) if self.training else 0.0
         dctx, seed = None, 0
         if p > 0.0:
@@ -273,7 +289,7 @@ class STGCN(nn.Module):
         params = self._params()
         x = x.contiguous().float()
         convs = (self.conv1, self.conv2, self.conv3, self.conv4)
-        ctxs = [cv.graph_context(x, edge_index) for cv in convs]
+        ctxs = [cv.graph_context(x, edge_index, edge_weight) for cv in convs]
         num_nodes = x.shape[0] // self.window_size
         if torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in params)):
             out = _STGCNFn.apply(x, convs, ctxs, dctx, p, seed, num_nodes, *params)
