@@ -127,6 +127,41 @@ int smaml_set_graph_weighted(smaml_ctx* ctx, const int64_t* edge_index_host, con
  * CSR, [4] k_gather_rows / k_gcn_dz launches that read a CSR of A_hat or A_hat^T of the CSR form. */
 int smaml_graph_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
 
+/* ---- weighted loss and weighted forecast scores -------------------------------------
+ * Training loss. A table holds nsets sets, each [Hf*N][C] floats in the layout of the targets y (row h'*N + n',
+ * column c). With a table the loss of every entry point below is inv * sum w (pred - y)^2 with the unchanged
+ * inv = 1 / (B * N * Hf * C): the library does not normalise (scale a table to mean 1 and losses, clip thresholds
+ * and learning rates keep their meaning). Per element, in f32: wd = w (p - y), loss += wd (p - y),
+ * dpred = dscale wd, and in the second-order sweep R dpred = dscale (w R p). Where w == 0 the element contributes
+ * exactly +0 to the loss, dpred and R dpred whatever y holds (NaN and infinity included); an all-ones table gives
+ * bitwise the results of no table.
+ * Which set a task reads: set 0 if nsets == 1; else the set with the task's index in the current smaml_set_tasks
+ * list: task z of smaml_meta_step / smaml_inner_loop reads set z, region r of smaml_adapt_steps_multi reads set
+ * tasks_host[r]; smaml_adapt_steps, smaml_adapt_steps_full and smaml_head_loss read set 0. With nsets > 1 and
+ * nsets != the number of registered tasks, smaml_meta_step, smaml_inner_loop and the smaml_adapt_steps* calls
+ * return SMAML_ESTATE naming both numbers before they launch anything.
+ * Scores. One node weight vector v[N] multiplies every summand of smaml_forecast [0..2], smaml_forecast_rollout
+ * [0..2], smaml_forecast_ensemble [0..3] and smaml_forecast_rollout_ensemble [0..3] by v[n'] of its target node,
+ * (v e) e for the squared terms, v |e|, v var and v CRPS for the others, the rollouts' gap rows included; v == 0
+ * gives exactly 0 whatever the target holds, all ones the unweighted bits. The fixed-order block and double sums
+ * are unchanged; pred, traj, mean, spread and member_* are not affected.
+ * State. Both tables survive smaml_set_tasks, smaml_set_graph[_weighted], smaml_set_gcn_params and smaml_reserve.
+ * Setting or clearing them drops no cache (the adaptation feature cache does not depend on the loss) and leaves a
+ * pending smaml_forward / smaml_backward pair valid. The caller does not set them while work that reads them is
+ * in flight, as for smaml_set_graph. smaml_set_dropout composes with them unchanged. */
+/* host-only: SMAML_EINVAL naming set and element for a negative, NaN or infinite weight, a set with no positive
+ * weight, nsets <= 0, w_host NULL. */
+int smaml_loss_weights_check(const smaml_dims* dims, const float* w_host, int32_t nsets);
+/* copies [nsets][Hf*N][C] into a buffer the context owns (freed by smaml_destroy); runs the check above first and
+ * leaves the live table alone if it fails; (NULL, 0) clears. Complete on return. */
+int smaml_set_loss_weights(smaml_ctx* ctx, const float* w_host, int32_t nsets);
+/* node weights [N] of the forecast score sums; same checks; NULL clears. */
+int smaml_set_score_weights(smaml_ctx* ctx, const float* node_w_host);
+/* (cap entries written, *count = 6) [0] loss sets held, [1] 1 if score weights are held, and since the last
+ * set/clear of either: [2] weighted k_head_loss launches, [3] weighted k_head_loss_small, [4] weighted k_head_dual,
+ * [5] weighted score launches. */
+int smaml_loss_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
+
 /* Frozen GCN parameters (flat, layout which=1), device pointer kept by reference. */
 int smaml_set_gcn_params(smaml_ctx* ctx, const float* gcn_flat);
 

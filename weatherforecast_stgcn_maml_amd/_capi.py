@@ -28,7 +28,8 @@ EXPORTS = (
     "smaml_adapt_steps_multi", "smaml_adapt_prepare_multi", "smaml_forecast_ensemble", "smaml_backward_base",
     "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
     "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats", "smaml_graph_csr", "smaml_set_graph_weighted",
-    "smaml_graph_stats",
+    "smaml_graph_stats", "smaml_loss_weights_check", "smaml_set_loss_weights", "smaml_set_score_weights",
+    "smaml_loss_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -148,6 +149,12 @@ ROLLOUT_ENSEMBLE_MAX_CYCLES = 1024  # the mask site's step 64 j + e has 16 bits
 _SIGS["smaml_graph_csr"] = ([PI64, PF32, I64, I32, PI32, PI32, PF32, I64, PI64], I32)
 _SIGS["smaml_set_graph_weighted"] = ([P, PI64, PF32, I64], I32)
 _SIGS["smaml_graph_stats"] = ([P, PI64, I32, PI32], I32)
+_SIGS["smaml_loss_weights_check"] = ([PDIMS, PF32, I32], I32)
+_SIGS["smaml_set_loss_weights"] = ([P, PF32, I32], I32)
+_SIGS["smaml_set_score_weights"] = ([P, PF32], I32)
+_SIGS["smaml_loss_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_loss_stats order (the tables held; weighted launches since the last set / clear of either table)
+LOSS_STATS = ("loss_sets", "score_weights", "head_loss", "head_loss_small", "head_dual", "score_launches")
 # smaml_graph_stats order (host counters of the live graph; form: 0 none, 1 ELL, 2 CSR)
 GRAPH_STATS = ("form", "entries", "longest_row", "csr_layer_launches", "csr_gather_launches")
 GRAPH_ELL, GRAPH_CSR = 1, 2
@@ -264,6 +271,28 @@ def set_graph_auto(ctx, edge_index, edge_weight=None, skip_same=False):
     return True
 
 
+def _loss_table(dims, w):
+    """``w`` as the contiguous float32 [nsets][Hf*N][C] array smaml_set_loss_weights reads (one table: nsets = 1)."""
+    rows, C = int(dims.forecast_horizon) * int(dims.num_nodes), int(dims.output_channels)
+    if hasattr(w, "detach"):
+        w = w.detach().cpu().numpy()
+    if isinstance(w, (list, tuple)):
+        w = np.stack([np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float32) for x in w])
+    a = np.ascontiguousarray(w, dtype=np.float32)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] != (rows, C) or a.shape[0] < 1:
+        raise ValueError(f"loss weights must be [{rows}, {C}] or [nsets, {rows}, {C}], got {tuple(a.shape)}")
+    return a
+
+
+def loss_weights_check(dims, w):
+    """smaml_loss_weights_check on the host: raises SmamlError naming the set and element of a bad weight."""
+    d = dims if isinstance(dims, Dims) else Dims.from_model(dims)
+    a = _loss_table(d, w)
+    check(lib().smaml_loss_weights_check(ctypes.byref(d), a.ctypes.data_as(PF32), a.shape[0]))
+
+
 def ptr(t) -> int:
     return t.data_ptr()
 
@@ -333,6 +362,36 @@ class Context:
         check(self._L.smaml_graph_stats(self._h, buf, n, ctypes.byref(cnt)))
         assert cnt.value == n, (cnt.value, n)
         return {name: int(buf[i]) for i, name in enumerate(GRAPH_STATS)}
+
+    def set_loss_weights(self, w):
+        """Loss weights (smaml_set_loss_weights): one table [Hf*N, C], one per task [nsets, Hf*N, C] (array, tensor
+        or a list of tables), or None to clear. Copied: the caller's array is free on return."""
+        if w is None:
+            check(self._L.smaml_set_loss_weights(self._h, None, 0))
+            return
+        a = _loss_table(self.dims, w)
+        check(self._L.smaml_set_loss_weights(self._h, a.ctypes.data_as(PF32), a.shape[0]))
+
+    def set_score_weights(self, v):
+        """Node weights [N] of the forecast score sums (smaml_set_score_weights), or None to clear."""
+        if v is None:
+            check(self._L.smaml_set_score_weights(self._h, None))
+            return
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        a = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        if a.size != int(self.dims.num_nodes):
+            raise ValueError(f"score weights must have {int(self.dims.num_nodes)} entries, got {a.size}")
+        check(self._L.smaml_set_score_weights(self._h, a.ctypes.data_as(PF32)))
+
+    def loss_stats(self):
+        """{counter: value} of the weight tables and their launches (smaml_loss_stats; host counters, no sync)."""
+        n = len(LOSS_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_loss_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(LOSS_STATS)}
 
     def set_gcn_params(self, flat):
         self._gcn = flat

@@ -97,7 +97,8 @@ class AdaptResult:
 def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_name: str, epochs: int = 15,
           max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
           val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
-          dropout_seed: int = 0, orders=None, train_base: bool = False, edge_weight=None) -> AdaptResult:
+          dropout_seed: int = 0, orders=None, train_base: bool = False, edge_weight=None,
+          loss_weights=None) -> AdaptResult:
     """``dropout`` = (STGCN dropout_rate, lstm_dropout) of the train-mode steps (the reference
     adapts in train mode: (0.2, 0.2)); validation runs without dropout (eval mode).
     ``orders``: optional per-epoch sample permutations of the training windows (default: drawn
@@ -106,7 +107,9 @@ def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_
     "for ALL parameters" announce and its ``no_grad`` withholds (F2): each epoch is one
     ``smaml_adapt_steps_full`` call, one Adam state and one joint gradient clip over both vectors, no
     per-window feature cache; ``AdaptResult.gcn`` is the adapted flat GCN vector and the validation runs on
-    the adapted base. ``edge_weight`` [E] (optional): the graph's edge weights, as PyG's ``GCNConv`` takes them."""
+    the adapted base. ``edge_weight`` [E] (optional): the graph's edge weights, as PyG's ``GCNConv`` takes them.
+    ``loss_weights`` ``[Hf*N, C]`` (``loss.make_loss_weights``): the training steps and the validation loss are
+    ``mean W (pred - y)^2`` (``smaml_set_loss_weights``); the context's table is cleared again before returning."""
     dev = torch.device(device)
     ctx = ctx or _capi.Context(dims, dev.index or 0)
     ei = edge_index.detach().cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
@@ -118,6 +121,21 @@ def adapt(dims: ModelDims, features, edge_index, gcn: dict, theta: dict, region_
     stream_t = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
     stream_t = stream_t.to(dev, torch.float32).contiguous()
     ctx.set_tasks([stream_t])
+    if loss_weights is not None and _capi._loss_table(dims, loss_weights).shape[0] != 1:
+        raise ValueError("adapt takes one loss weight table [Hf*N, C]")
+    if loss_weights is not None:
+        ctx.set_loss_weights(loss_weights)
+    try:
+        return _adapt_epochs(dims, ctx, stream_t, th, gflat, region_name, epochs, max_samples, train_frac, base_lr, dev,
+                             val_batch, dropout, dropout_seed, orders, train_base)
+    finally:
+        if loss_weights is not None:
+            ctx.set_loss_weights(None)
+
+
+def _adapt_epochs(dims, ctx, stream_t, th, gflat, region_name, epochs, max_samples, train_frac, base_lr, dev, val_batch,
+                  dropout, dropout_seed, orders, train_base) -> AdaptResult:
+    """``adapt``'s epochs and validation on a prepared context (graph, parameters, task and loss weights set)."""
     n_all = synth.num_samples(stream_t.shape[0], dims.window_size, dims.forecast_horizon)
     n_max = min(max_samples, n_all)
     n_train = int(train_frac * n_max)
@@ -190,7 +208,7 @@ def check_orders(orders, n_trains, epochs: int) -> List[np.ndarray]:
 def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, region_names, epochs: int = 15,
                max_samples: int = 1200, train_frac: float = 0.8, base_lr: float = 0.0006, device="cuda",
                val_batch: int = 32, ctx: Optional[_capi.Context] = None, dropout=(0.0, 0.0),
-               dropout_seed: int = 0, orders=None, edge_weight=None) -> List[AdaptResult]:
+               dropout_seed: int = 0, orders=None, edge_weight=None, loss_weights=None) -> List[AdaptResult]:
     """``adapt`` for several regions at once (main.py adapts its regions one after another): every region
     starts from the same meta-trained ``theta`` and keeps its own stream, climate optimiser settings,
     ``ClimateAwareLRScheduler`` (stepped on its own epoch mean), shuffle orders and Adam state, and each
@@ -198,7 +216,9 @@ def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, reg
     are grouped by their number of training windows (lockstep needs equal step counts); the groups run
     one after another. Region r computes what ``adapt`` computes on its stream alone.
     ``orders[r][epoch]``: optional shuffle orders; default: drawn from the global torch RNG region by
-    region, each region's epochs in turn -- the draws of one ``adapt`` call per region in that order."""
+    region, each region's epochs in turn -- the draws of one ``adapt`` call per region in that order.
+    ``loss_weights``: one table ``[Hf*N, C]`` for every region or one per region ``[R, Hf*N, C]``, as in ``adapt``
+    (the validation loss is then the weighted mean too, formed from ``smaml_forecast``'s predictions)."""
     dev = torch.device(device)
     R = len(streams)
     if len(region_names) != R or R == 0:
@@ -216,6 +236,24 @@ def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, reg
         stream_ts.append(t.to(dev, torch.float32).contiguous())
     ctx.set_tasks(stream_ts)
     ctx.set_task_ids([0] * R)  # every region draws the dropout masks of a single-region adapt()
+    lw = None
+    if loss_weights is not None:
+        lw = _capi._loss_table(dims, loss_weights)
+        if lw.shape[0] not in (1, R):
+            raise ValueError(f"{lw.shape[0]} loss weight tables for {R} regions (one table, or one per region)")
+        ctx.set_loss_weights(lw)
+    try:
+        return _adapt_many_groups(dims, ctx, stream_ts, th0, region_names, epochs, max_samples, train_frac, base_lr,
+                                  dev, val_batch, dropout, dropout_seed, orders, lw)
+    finally:
+        if lw is not None:
+            ctx.set_loss_weights(None)
+
+
+def _adapt_many_groups(dims, ctx, stream_ts, th0, region_names, epochs, max_samples, train_frac, base_lr, dev,
+                       val_batch, dropout, dropout_seed, orders, lw) -> List[AdaptResult]:
+    """``adapt_many``'s lockstep groups on a prepared context (graph, parameters, tasks and loss weights set)."""
+    R = len(stream_ts)
     n_maxs = [min(max_samples, synth.num_samples(t.shape[0], dims.window_size, dims.forecast_horizon))
               for t in stream_ts]
     n_trains = [int(train_frac * n) for n in n_maxs]
@@ -253,17 +291,36 @@ def adapt_many(dims: ModelDims, streams, edge_index, gcn: dict, theta: dict, reg
                 lrs[i] = scheds[i].step(float(avgs[i]))
         ctx.set_dropout(0.0, 0.0, 0)
         for i, r in enumerate(group):
-            res[i].val_loss = evaluate_region(ctx, th[i], r, list(range(n_train, n_maxs[r])), val_batch)
+            res[i].val_loss = evaluate_region(ctx, th[i], r, list(range(n_train, n_maxs[r])), val_batch,
+                                              loss_weights=None if lw is None else lw[r if lw.shape[0] > 1 else 0],
+                                              features=stream_ts[r])
             results[r] = res[i]
     return results
 
 
-def evaluate_region(ctx: _capi.Context, theta: torch.Tensor, task: int, sample_ids, batch: int = 32) -> float:
+def evaluate_region(ctx: _capi.Context, theta: torch.Tensor, task: int, sample_ids, batch: int = 32,
+                    loss_weights=None, features=None) -> float:
     """Mean per-sample MSE over the given windows of task ``task`` (no gradients, no dropout): the
-    squared-error sum of ``smaml_forecast`` over the element count."""
+    squared-error sum of ``smaml_forecast`` over the element count. With ``loss_weights [Hf*N, C]`` the weighted
+    mean ``mean W (pred - y)^2``, formed in torch from ``smaml_forecast``'s predictions and the targets in
+    ``features`` (the task's stream on the device)."""
     if len(sample_ids) == 0:
         return 0.0
     d = ctx.dims
+    if loss_weights is not None:
+        from .loss import weighted_mse_reference
+
+        T, Hf, N, C = d.window_size, d.forecast_horizon, d.num_nodes, d.output_channels
+        ids = np.asarray(sample_ids, np.int32)
+        W = torch.as_tensor(np.asarray(loss_weights, np.float32), device=theta.device)
+        total = 0.0
+        for i in range(0, len(ids), batch):
+            chunk = ids[i:i + batch]
+            pred = torch.empty(len(chunk), N * Hf, C, device=theta.device)
+            ctx.forecast(_capi.stream_ptr(torch), theta, chunk, batch, task=task, pred=pred)
+            y = torch.stack([features[int(w) + T + 1:int(w) + T + 1 + Hf, :, :C].reshape(Hf * N, C) for w in chunk])
+            total += float(weighted_mse_reference(pred.double(), y.double(), W.double()).item()) * len(chunk)
+        return total / len(ids)
     sums = torch.empty(3, d.forecast_horizon, d.output_channels, device=theta.device, dtype=torch.float64)
     ctx.forecast(_capi.stream_ptr(torch), theta, np.asarray(sample_ids, np.int32), batch, task=task, skill=sums)
     return float(sums[0].sum().item()) / (len(sample_ids) * d.num_nodes * d.forecast_horizon * d.output_channels)

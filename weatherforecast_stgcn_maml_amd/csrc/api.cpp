@@ -382,6 +382,14 @@ struct smaml_ctx {
   int gcn_dz_fused = 0;
   int64_t af_stats[6] = {};  // smaml_adapt_full_stats: counters of the last smaml_adapt_steps_full call
   const float* gcn = nullptr;
+  // Loss weights (smaml_set_loss_weights): lw_sets tables [Hf*N][C] in lw_buf; the set index of each region of
+  // the running smaml_adapt_steps_multi call in lw_zset; node weights [N] of the forecast score sums in sw_buf
+  // (smaml_set_score_weights). lw_count: smaml_loss_stats [2] .. [5]. None of these lives in the arena: they
+  // survive smaml_reserve, smaml_set_tasks and the graph and parameter setters.
+  HipBuf lw_buf, lw_zset, sw_buf;
+  int lw_sets = 0;
+  bool sw_set = false;
+  int64_t lw_count[4] = {};
   // workspace
   HipBuf arena;
   int zb_cap = 0, z_cap = 0;
@@ -754,9 +762,36 @@ void set_work(smaml_ctx* c, int Z, int B) {
   c->w.consec = 0;
   c->w.fcompact = 0;
   c->w.drop = Drop{};  // dropout only inside smaml_meta_step / smaml_adapt_steps (set_step_drop)
+  c->w.lw = LossW{};   // loss weights only where an entry point asks for them (use_loss_weights)
   c->w.vcount = c->vcount;
   c->w.kn = c->kn;
   if (c->Hs_main) use_primal(c, SET_MAIN);
+}
+
+// The loss weights of a compute call that reads the registered tasks: more than one set must be one per task.
+int check_loss_weights(const smaml_ctx* c, const char* who) {
+  if (c->lw_sets > 1 && c->lw_sets != (int)c->feats.size())
+    return fail(SMAML_ESTATE, std::string(who) + ": " + std::to_string(c->lw_sets) + " loss weight sets held but " +
+                                  std::to_string(c->feats.size()) + " tasks registered (one set, or one per task)");
+  return SMAML_OK;
+}
+
+// Points the workspace's head launches at the live table (after set_work, which clears it): task z of the launch
+// reads set zset[z] (a device table), or set z without one; a single set is shared by every task.
+void use_loss_weights(smaml_ctx* c, const int32_t* zset) {
+  if (c->lw_sets <= 0) return;
+  LossW& lw = c->w.lw;
+  lw.w = c->lw_buf.as<float>();
+  lw.zstride = c->lw_sets > 1 ? (int64_t)c->d.Hf * c->d.N * c->d.C : 0;
+  lw.zset = c->lw_sets > 1 ? zset : nullptr;
+  lw.count = c->lw_count;
+}
+
+// The node weights of the forecast score sums, or null; counts the launch that reads them.
+const float* score_weights(smaml_ctx* c) {
+  if (!c->sw_set) return nullptr;
+  ++c->lw_count[3];
+  return c->sw_buf.as<float>();
 }
 
 #define TIMED(c, s, cat, fl, stmt)                              \
@@ -1511,7 +1546,8 @@ int forecast_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
   TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
         launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
   if (skill)
-    TIMED(c, s, C_MISC, 0, launch_skill_sums(s, d, B, pred, xt, scale_dev, c->fc_part.as<float>(), skill, first));
+    TIMED(c, s, C_MISC, 0,
+          launch_skill_sums(s, d, B, pred, xt, scale_dev, c->fc_part.as<float>(), skill, first, score_weights(c)));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -1661,7 +1697,7 @@ int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* 
   }
   TIMED(c, s, C_MISC, 0,
         launch_ens_stats(s, d, B, E, P, xt, scale_dev, mean, spread, member_pred, a.nwin * d.N * d.HfC,
-                         c->fc_part.as<float>(), scores, a.done == 0));
+                         c->fc_part.as<float>(), scores, a.done == 0, scores ? score_weights(c) : nullptr));
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
@@ -2002,6 +2038,67 @@ int smaml_graph_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t*
   if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad graph_stats arguments");
   for (int i = 0; i < 5 && i < cap; ++i) counts[i] = c->graph_stats[i];
   if (count) *count = 5;
+  return SMAML_OK;
+}
+
+// One weight vector: every entry finite and >= 0, at least one positive. `what` names it in the message.
+static int check_weights(const float* w, int64_t n, const std::string& what) {
+  bool positive = false;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!(w[i] >= 0.f) || std::isinf(w[i]))
+      return fail(SMAML_EINVAL, what + " element " + std::to_string(i) + " is " + std::to_string(w[i]) +
+                                    " (weights are finite and >= 0)");
+    positive = positive || w[i] > 0.f;
+  }
+  if (!positive) return fail(SMAML_EINVAL, what + " has no positive weight");
+  return SMAML_OK;
+}
+
+int smaml_loss_weights_check(const smaml_dims* dims, const float* w_host, int32_t nsets) {
+  if (!dims || !w_host) return fail(SMAML_EINVAL, "smaml_loss_weights_check: NULL argument");
+  if (nsets <= 0) return fail(SMAML_EINVAL, "smaml_loss_weights_check: nsets must be positive");
+  const int64_t per = (int64_t)dims->forecast_horizon * dims->num_nodes * dims->output_channels;
+  if (per <= 0) return fail(SMAML_EINVAL, "smaml_loss_weights_check: bad dims");
+  for (int32_t z = 0; z < nsets; ++z)
+    TRY(check_weights(w_host + (int64_t)z * per, per, "loss weights: set " + std::to_string(z)));
+  return SMAML_OK;
+}
+
+int smaml_set_loss_weights(smaml_ctx* c, const float* w_host, int32_t nsets) {
+  if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  if (w_host || nsets != 0) {
+    TRY(smaml_loss_weights_check(&c->dims, w_host, nsets));  // (a failure leaves the live table alone)
+    TRY(ensure_device(c));
+    const int64_t bytes = (int64_t)nsets * c->d.Hf * c->d.N * c->d.C * 4;
+    HIP_TRY(hipDeviceSynchronize());  // (nothing that reads the old table is in flight)
+    HIP_TRY(c->lw_buf.grow(bytes));
+    HIP_TRY(hipMemcpy(c->lw_buf.ptr, w_host, (size_t)bytes, hipMemcpyHostToDevice));
+  }
+  c->lw_sets = w_host ? nsets : 0;
+  c->w.lw = LossW{};
+  for (auto& x : c->lw_count) x = 0;
+  return SMAML_OK;
+}
+
+int smaml_set_score_weights(smaml_ctx* c, const float* node_w_host) {
+  if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  if (node_w_host) {
+    TRY(check_weights(node_w_host, c->d.N, "score weights:"));
+    TRY(ensure_device(c));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(c->sw_buf.grow((int64_t)c->d.N * 4));
+    HIP_TRY(hipMemcpy(c->sw_buf.ptr, node_w_host, (size_t)c->d.N * 4, hipMemcpyHostToDevice));
+  }
+  c->sw_set = node_w_host != nullptr;
+  for (auto& x : c->lw_count) x = 0;
+  return SMAML_OK;
+}
+
+int smaml_loss_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad loss_stats arguments");
+  const int64_t v[6] = {c->lw_sets, c->sw_set ? 1 : 0, c->lw_count[0], c->lw_count[1], c->lw_count[2], c->lw_count[3]};
+  for (int i = 0; i < 6 && i < cap; ++i) counts[i] = v[i];
+  if (count) *count = 6;
   return SMAML_OK;
 }
 
@@ -2365,7 +2462,8 @@ int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan
     c->ro_stats[4] += 1;
     if (skill)
       TIMED(c, s, C_MISC, 0,
-            launch_rollout_skill(s, ra, j, p.R, out, ostride, scale_dev, c->fc_part.as<float>(), skill, done == 0));
+            launch_rollout_skill(s, ra, j, p.R, out, ostride, scale_dev, c->fc_part.as<float>(), skill, done == 0,
+                                 score_weights(c)));
     c->ro_stats[0] += 1;
   }
   HIP_TRY(hipGetLastError());
@@ -2717,7 +2815,8 @@ int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p
     const int64_t off = done * p.R * blkf;
     TIMED(c, s, C_MISC, 0,
           launch_rens_stats(s, d, B, E, p.R * sl, traj, tstride, src, scale_dev, mean ? mean + off : nullptr,
-                            spread ? spread + off : nullptr, c->fc_part.as<float>(), scores, done == 0));
+                            spread ? spread + off : nullptr, c->fc_part.as<float>(), scores, done == 0,
+                            scores ? score_weights(c) : nullptr));
   }
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
@@ -2936,6 +3035,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   TRY(require_ready(c));
   TRY(check_lstm_dims(c->dims, "smaml_meta_step"));
   if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  TRY(check_loss_weights(c, "smaml_meta_step"));
   if (!theta || steps < 0 || batch <= 0 || !windows_host) return fail(SMAML_EINVAL, "bad meta_step arguments");
   if (order < 0 || order > 2) return fail(SMAML_EINVAL, "order must be 0, 1 or 2");
   if (order >= 1 && !meta_grad) return fail(SMAML_EINVAL, "meta_grad required for order >= 1");
@@ -2950,6 +3050,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   if (order == 2) TRY(ensure_so_store(c, std::max(steps, 1), Z, B));
   if (order == 2) TRY(ensure_keep(c, steps, Z, B));
   set_work(c, Z, B);
+  use_loss_weights(c, nullptr);  // task z reads set z
   const int nkeep = order == 2 ? std::min(std::min(c->keep_n, c->keep_want), steps) : 0;
   c->keep_last = nkeep;
   // sample window table for every step (support steps then the query batch)
@@ -3272,6 +3373,7 @@ static int adapt_run(smaml_ctx* c, hipStream_t s, const AdaptCall& a) {
   const int B = a.B, R = a.R, nsteps = a.nsteps;
   const bool train = a.gcn != nullptr;
   if (train && R != 1) return fail(SMAML_EINVAL, "internal: adapt_run trains the base of one region only");
+  TRY(check_loss_weights(c, a.name_regions ? "smaml_adapt_steps_multi" : "smaml_adapt_steps"));
   // one table for the call: the window pointers [nsteps][R][B], then (cache) the slot pointers [nsteps][R]
   const int64_t nwin = (int64_t)nsteps * R * B, nslot = (int64_t)nsteps * R;
   std::vector<const float*> ptrs(nwin);
@@ -3309,6 +3411,10 @@ static int adapt_run(smaml_ctx* c, hipStream_t s, const AdaptCall& a) {
     for (int r = 0; r < R; ++r) ids[r] = a.tasks[r] < (int)c->task_ids.size() ? c->task_ids[a.tasks[r]] : a.tasks[r];
     TRY(c->stage.upload(s, c->task_id_dev, ids.data(), (int64_t)R * 4));
   }
+  if (c->lw_sets > 1) {  // region r reads the set of its task index (a single region: task 0, set 0)
+    HIP_TRY(c->lw_zset.grow((int64_t)R * 4));
+    TRY(c->stage.upload(s, c->lw_zset.ptr, a.tasks, (int64_t)R * 4));
+  }
   // Batch-1 steps without GCN dropout reuse each window's GCN features across epochs (F2; cache implies B = 1).
   auto t0 = clk::now();
   if (cache) {
@@ -3326,6 +3432,7 @@ static int adapt_run(smaml_ctx* c, hipStream_t s, const AdaptCall& a) {
     for (int r0 = 0; r0 < R; r0 += G) {
       const int Z = std::min(G, R - r0);
       set_work(c, Z, B);  // (ends a pending smaml_forward / smaml_backward pair)
+      use_loss_weights(c, c->lw_sets > 1 ? c->lw_zset.as<int32_t>() + r0 : nullptr);
       Work& w = c->w;
       // (one region: the parameters at stride 0)
       float* th = a.theta + (int64_t)r0 * P;
@@ -3811,6 +3918,11 @@ int smaml_head_loss(smaml_ctx* c, void* stream, const float* theta, const float*
   const int act = c->act_B;
   const Work saved = c->w;
   set_work(c, 1, nsamples);
+  if (c->lw_sets > 0) {  // set 0, whatever the number of sets
+    use_loss_weights(c, nullptr);
+    c->w.lw.zstride = 0;
+    c->w.lw.zset = nullptr;
+  }
   if (y_host) {
     for (int i = 0; i < nsamples; ++i)
       if (!y_host[i]) return fail(SMAML_EINVAL, "null target pointer");

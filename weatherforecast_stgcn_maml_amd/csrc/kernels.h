@@ -233,8 +233,19 @@ __host__ __device__ inline int64_t xg_dedup_rows(int B, int T, int N) { return (
 // first row of step t's block of window rows in a task's XgDedup table (M = B N)
 __host__ __device__ inline int64_t xg_dedup_row0(int t, int M, int N) { return t == 0 ? 0 : (int64_t)M + (int64_t)(t - 1) * N; }
 
+// Loss weights of the head kernels (smaml_set_loss_weights): task z reads the table [Hf*N][C] (the layout of
+// the targets y) at w + (zset ? zset[z] : z) * zstride; zstride 0: one set shared by every task. w null: the
+// unweighted kernels. count: [0] k_head_loss, [1] k_head_loss_small, [2] k_head_dual weighted launches (host).
+struct LossW {
+  const float* w = nullptr;
+  int64_t zstride = 0;
+  const int32_t* zset = nullptr;
+  int64_t* count = nullptr;
+};
+
 struct Work {
   int Z = 0, B = 0, M = 0;
+  LossW lw{};               // set per call by the entry points that compute a loss (set_work clears it)
   BwdImgs bimg{};           // pre-split BPTT weight images (launch_split_bwd), small-grid BPTT only
   const float* bimg_src = nullptr; // the parameter vector bimg.th was split from
   const float* xg = nullptr;       // small-grid forward: layer 0's input projection F . W_ih0^T for all steps
@@ -275,6 +286,9 @@ struct Work {
 
 inline void count_variant(const Work& w, Variant v) {
   if (w.vcount) ++w.vcount[v];
+}
+inline void count_loss_w(const LossW& lw, int kernel) {
+  if (lw.count) ++lw.count[kernel];
 }
 
 constexpr int SQB = 64;  // blocks per task for squared-norm partials
@@ -493,7 +507,7 @@ void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, boo
 // overwritten). launch_skill_sums's scheme: fixed order, no atomics.
 int rollout_skill_blocks(const Dims& d, int B);
 void launch_rollout_skill(hipStream_t s, const RollArgs& a, int j, int R, const float* blk, int64_t blk_stride,
-                          const float* scale, float* part, double* skill, bool first);
+                          const float* scale, float* part, double* skill, bool first, const float* vw = nullptr);
 // out[z] = layer-0 input projection of every distinct stream row of task z's consecutive windows
 // (XgDedup layout) with the gate weights W_ih0 of `params` (theta or the tangent direction U); the
 // weights come from the pre-split images `img` when given (w.gimg.th / .u), else from `params`; F is
@@ -541,18 +555,19 @@ void launch_ens_dropout(hipStream_t s, float* x, int64_t n, int G, uint32_t seed
                         uint32_t thr, float sc, uint64_t base);
 // Mean, spread, member copies and the four sums of one pass from its member predictions P [E][B][N*Hf][C]
 // (k_ens_stats): part [skill_blocks][HfC][4] f32 partials, added in double onto scores [4][Hf][C] (first:
-// overwritten). Any of mean / spread / member_pred / scores may be null.
+// overwritten). Any of mean / spread / member_pred / scores may be null. vw: node weights [N] of the sums
+// (smaml_set_score_weights) or null, here and in the other three score launchers.
 hipError_t ens_stats_prepare();  // raise k_ens_stats's dynamic-LDS limit on the current device (needed above E = 32)
 void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P, const float* const* xtab,
                       const float* scale, float* mean, float* spread, float* member_pred, int64_t mstride, float* part,
-                      double* scores, bool first);
+                      double* scores, bool first, const float* vw = nullptr);
 // Ensemble-rollout statistics of one pass (k_rens_stats): X [E][B][Q][N][C] (Q = R (Hf + 1) trajectory rows per
 // origin, member stride estride) against src[b] = the origin's stream rows; mean / spread [B][Q][N][C]; part
 // [skill_blocks][Q C][4] f32 partials, added in double onto scores [4][Q][C] (first: overwritten).
 hipError_t rens_stats_prepare();  // as ens_stats_prepare, for k_rens_stats
 void launch_rens_stats(hipStream_t s, const Dims& d, int B, int E, int Q, const float* X, int64_t estride,
                        const float* const* src, const float* scale, float* mean, float* spread, float* part,
-                       double* scores, bool first);
+                       double* scores, bool first, const float* vw = nullptr);
 // launch_head_loss's prediction alone from given h_T rows (hz floats between tasks) into pred [Z][M][HfC]
 void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
                       int64_t tstride, const ParamOff& po, float* pred);
@@ -561,7 +576,7 @@ void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* 
 // (first: overwritten). Fixed order, no atomics.
 int skill_blocks(const Dims& d, int B);
 void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, const float* const* xtab,
-                       const float* scale, float* part, double* skill, bool first);
+                       const float* scale, float* part, double* skill, bool first, const float* vw = nullptr);
 void launch_head_loss(hipStream_t s, const Dims& d, const Work& w, const float* theta, int64_t tstride,
                       const ParamOff& po, const float* const* xtab, float dscale, bool want_loss);
 void launch_head_loss_y(hipStream_t s, const Dims& d, const Work& w, const float* hT, const float* theta,

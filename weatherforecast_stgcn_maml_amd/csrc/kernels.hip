@@ -1209,13 +1209,17 @@ void launch_split_gate(hipStream_t s, const Dims& d, const ParamOff& po, const f
 // Head + loss: pred[m, c'] = h_T[m] . Wo[c'] + bo[c'];  loss = mean (pred - y)^2 with the
 // F4 pairing: pred row (n*Hf + h) of sample s is compared with target row (h'*N + n')
 // of the SAME flat row index r = n*Hf + h  (h' = r / N, n' = r % N).
+// WT: the weighted loss mean w (pred - y)^2, w = the task's table (LossW) at the target's own index
+// (h' N + n') C + c: wd = w (p - y), loss += wd (p - y), dpred = dscale wd. w == 0 selects +0 for all three,
+// whatever y holds; w == 1 gives the unweighted kernel's bits.
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_head_loss(const float* __restrict__ hT_base, int64_t hT_zstride,
                                                   const float* __restrict__ theta, int64_t tstride, int64_t wo,
                                                   int64_t bo, const float* const* __restrict__ xtab,
                                                   float* __restrict__ pred, float* __restrict__ dpred,
                                                   float* __restrict__ lpart, int lblocks, int M, int H,
                                                   int HfC, int N, int Hf, int C, int yrow0, int yld, int B,
-                                                  float dscale) {
+                                                  float dscale, LossW lw) {
   __shared__ float smem[CfgNT::SMEM_FLOATS];
   const int z = blockIdx.z;
   const float* th = theta + (int64_t)z * tstride;
@@ -1226,6 +1230,8 @@ __global__ __launch_bounds__(NT) void k_head_loss(const float* __restrict__ hT_b
   acc.zero();
   gemm_mainloop<CfgNT>(la, lb, m0, 0, 0, H, acc, smem);
   float lsum = 0.f;
+  const float* lwz = nullptr;
+  if constexpr (WT) lwz = lw.w + (int64_t)(lw.zset ? lw.zset[z] : z) * lw.zstride;
 #pragma unroll
   for (int i = 0; i < CfgNT::WTM; ++i)
 #pragma unroll
@@ -1248,8 +1254,16 @@ __global__ __launch_bounds__(NT) void k_head_loss(const float* __restrict__ hT_b
           const float* xs = xtab[z * B + s];
           const float y = xs[((int64_t)(yrow0 + hp) * N + np) * yld + c];
           const float df = p - y;
-          lsum = fmaf(df, df, lsum);
-          if (dpred) dpred[o] = dscale * df;
+          if constexpr (WT) {
+            const float wv = lwz[((int64_t)hp * N + np) * C + c];
+            const bool on = wv != 0.f;
+            const float wd = on ? wv * df : 0.f;
+            lsum = on ? fmaf(wd, df, lsum) : lsum;
+            if (dpred) dpred[o] = dscale * wd;
+          } else {
+            lsum = fmaf(df, df, lsum);
+            if (dpred) dpred[o] = dscale * df;
+          }
         }
       }
     }
@@ -1305,13 +1319,15 @@ const float* head_input(const Dims& d, const Work& w, bool tangent, int64_t* zst
 // Small-M head (batch-1 adaptation: M = 441 rows): the MFMA tile kernel above gets ceil(M/128)
 // workgroups and a serial epilogue. Here one workgroup per row m (one thread per output column):
 // h_T[m] is staged in LDS, each thread streams its Wo row (L2-resident) with all loads in flight.
-// Loss partial per row (head_lblocks = M), summed in row order by k_loss_final.
+// Loss partial per row (head_lblocks = M), summed in row order by k_loss_final. WT: as in k_head_loss.
+template <bool WT>
 __global__ __launch_bounds__(128) void k_head_loss_small(const float* __restrict__ hT_base, int64_t hT_zstride,
                                                          const float* __restrict__ theta, int64_t tstride, int64_t wo,
                                                          int64_t bo, const float* const* __restrict__ xtab,
                                                          float* __restrict__ pred, float* __restrict__ dpred,
                                                          float* __restrict__ lpart, int lblocks, int M, int H, int HfC,
-                                                         int N, int Hf, int C, int yrow0, int yld, int B, float dscale) {
+                                                         int N, int Hf, int C, int yrow0, int yld, int B, float dscale,
+                                                         LossW lw) {
   __shared__ __attribute__((aligned(16))) float hs[SMAML_HEAD_MAX_H];  // read as float4
   __shared__ float red[2];
   const int z = blockIdx.z, m = blockIdx.x, cc = threadIdx.x;
@@ -1339,8 +1355,17 @@ __global__ __launch_bounds__(128) void k_head_loss_small(const float* __restrict
       const int rr = n * Hf + hh;  // F4 pairing (see k_head_loss)
       const int hp = rr / N, np = rr - hp * N;
       const float df = p - xtab[z * B + sm][((int64_t)(yrow0 + hp) * N + np) * yld + c];
-      lsum = df * df;
-      if (dpred) dpred[o] = dscale * df;
+      if constexpr (WT) {
+        const float* lwz = lw.w + (int64_t)(lw.zset ? lw.zset[z] : z) * lw.zstride;
+        const float wv = lwz[((int64_t)hp * N + np) * C + c];
+        const bool on = wv != 0.f;
+        const float wd = on ? wv * df : 0.f;
+        lsum = on ? wd * df : 0.f;
+        if (dpred) dpred[o] = dscale * wd;
+      } else {
+        lsum = df * df;
+        if (dpred) dpred[o] = dscale * df;
+      }
     }
   }
   if (lpart) {
@@ -1427,33 +1452,66 @@ void launch_head_loss(hipStream_t s, const Dims& d, const Work& w, const float* 
   if (w.drop.lstm()) launch_drop_rows(s, w, d.H, top + (int64_t)(d.T - 1) * w.M * d.H, (int64_t)d.T * w.M * d.H, w.hTd);
   int64_t hz = 0;
   const float* hT = head_input(d, w, false, &hz);
+  const bool wt = want_loss && xtab && w.lw.w;  // the weighted instantiation (LossW) only where a loss is formed
   if (head_small(d, w.M)) {
-    k_head_loss_small<<<dim3(w.M, 1, w.Z), head_small_threads(d), 0, s>>>(
-        hT, hz, theta, tstride, po.wo, po.bo, want_loss ? xtab : nullptr, w.pred, want_loss ? w.dpred : nullptr,
-        want_loss ? w.lpart : nullptr, w.lblocks, w.M, d.H, d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, dscale);
+#define SMAML_HEAD_SMALL(WT_)                                                                                      \
+  k_head_loss_small<WT_><<<dim3(w.M, 1, w.Z), head_small_threads(d), 0, s>>>(                                       \
+      hT, hz, theta, tstride, po.wo, po.bo, want_loss ? xtab : nullptr, w.pred, want_loss ? w.dpred : nullptr,      \
+      want_loss ? w.lpart : nullptr, w.lblocks, w.M, d.H, d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, dscale, w.lw)
+    if (wt) {
+      SMAML_HEAD_SMALL(true);
+      count_loss_w(w.lw, 1);
+    } else {
+      SMAML_HEAD_SMALL(false);
+    }
+#undef SMAML_HEAD_SMALL
     return;
   }
   dim3 grid((w.M + CfgNT::BM - 1) / CfgNT::BM, 1, w.Z);
   // targets from the feature stream: rows T+1 .. T+Hf after the window start, first C channels (F5)
-  k_head_loss<<<grid, NT, 0, s>>>(hT, hz, theta, tstride, po.wo, po.bo,
-                                  want_loss ? xtab : nullptr, w.pred, want_loss ? w.dpred : nullptr,
-                                  want_loss ? w.lpart : nullptr, w.lblocks, w.M, d.H, d.HfC, d.N, d.Hf,
-                                  d.C, d.T + 1, d.Cin0, w.B, dscale);
+#define SMAML_HEAD_BIG(WT_)                                                                                \
+  k_head_loss<WT_><<<grid, NT, 0, s>>>(hT, hz, theta, tstride, po.wo, po.bo, want_loss ? xtab : nullptr, w.pred, \
+                                       want_loss ? w.dpred : nullptr, want_loss ? w.lpart : nullptr, w.lblocks,  \
+                                       w.M, d.H, d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, dscale, w.lw)
+  if (wt) {
+    SMAML_HEAD_BIG(true);
+    count_loss_w(w.lw, 0);
+  } else {
+    SMAML_HEAD_BIG(false);
+  }
+#undef SMAML_HEAD_BIG
 }
 
 void launch_head_loss_y(hipStream_t s, const Dims& d, const Work& w, const float* hT, const float* theta,
                         const ParamOff& po, const float* const* ytab, float* pred, float* dpred, float dscale) {
   // explicit targets: ytab[s] -> y [Hf*N][C] in the reference's layout (dataset.py:40-48)
+  const bool wt = ytab && w.lw.w;
   if (head_small(d, w.M)) {
-    k_head_loss_small<<<dim3(w.M, 1, 1), head_small_threads(d), 0, s>>>(
-        hT, 0, theta, 0, po.wo, po.bo, ytab, pred, ytab ? dpred : nullptr, ytab ? w.lpart : nullptr, w.lblocks, w.M,
-        d.H, d.HfC, d.N, d.Hf, d.C, 0, d.C, w.B, dscale);
+#define SMAML_HEAD_SMALL(WT_)                                                                                        \
+  k_head_loss_small<WT_><<<dim3(w.M, 1, 1), head_small_threads(d), 0, s>>>(                                           \
+      hT, 0, theta, 0, po.wo, po.bo, ytab, pred, ytab ? dpred : nullptr, ytab ? w.lpart : nullptr, w.lblocks, w.M, \
+      d.H, d.HfC, d.N, d.Hf, d.C, 0, d.C, w.B, dscale, w.lw)
+    if (wt) {
+      SMAML_HEAD_SMALL(true);
+      count_loss_w(w.lw, 1);
+    } else {
+      SMAML_HEAD_SMALL(false);
+    }
+#undef SMAML_HEAD_SMALL
     return;
   }
   dim3 grid((w.M + CfgNT::BM - 1) / CfgNT::BM, 1, 1);
-  k_head_loss<<<grid, NT, 0, s>>>(hT, 0, theta, 0, po.wo, po.bo, ytab, pred, ytab ? dpred : nullptr,
-                                  ytab ? w.lpart : nullptr, w.lblocks, w.M, d.H, d.HfC, d.N, d.Hf, d.C, 0, d.C,
-                                  w.B, dscale);
+#define SMAML_HEAD_BIG(WT_)                                                                                   \
+  k_head_loss<WT_><<<grid, NT, 0, s>>>(hT, 0, theta, 0, po.wo, po.bo, ytab, pred, ytab ? dpred : nullptr,       \
+                                       ytab ? w.lpart : nullptr, w.lblocks, w.M, d.H, d.HfC, d.N, d.Hf, d.C, 0, \
+                                       d.C, w.B, dscale, w.lw)
+  if (wt) {
+    SMAML_HEAD_BIG(true);
+    count_loss_w(w.lw, 0);
+  } else {
+    SMAML_HEAD_BIG(false);
+  }
+#undef SMAML_HEAD_BIG
 }
 
 __global__ void k_loss_final(const float* __restrict__ lpart, int lblocks, float inv_count,
@@ -1475,14 +1533,14 @@ void launch_loss_final(hipStream_t s, const Work& w, float inv_count, float* out
 void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* hT, int64_t hz, const float* theta,
                       int64_t tstride, const ParamOff& po, float* pred) {
   if (head_small(d, w.M)) {
-    k_head_loss_small<<<dim3(w.M, 1, w.Z), head_small_threads(d), 0, s>>>(
+    k_head_loss_small<false><<<dim3(w.M, 1, w.Z), head_small_threads(d), 0, s>>>(
         hT, hz, theta, tstride, po.wo, po.bo, nullptr, pred, nullptr, nullptr, 0, w.M, d.H, d.HfC, d.N, d.Hf, d.C,
-        d.T + 1, d.Cin0, w.B, 0.f);
+        d.T + 1, d.Cin0, w.B, 0.f, LossW{});
     return;
   }
   dim3 grid((w.M + CfgNT::BM - 1) / CfgNT::BM, 1, w.Z);
-  k_head_loss<<<grid, NT, 0, s>>>(hT, hz, theta, tstride, po.wo, po.bo, nullptr, pred, nullptr, nullptr, 0, w.M, d.H,
-                                  d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, 0.f);
+  k_head_loss<false><<<grid, NT, 0, s>>>(hT, hz, theta, tstride, po.wo, po.bo, nullptr, pred, nullptr, nullptr, 0, w.M,
+                                         d.H, d.HfC, d.N, d.Hf, d.C, d.T + 1, d.Cin0, w.B, 0.f, LossW{});
 }
 
 // ---- forecast skill sums (smaml_forecast) ---------------------------------------------------------
@@ -1494,10 +1552,14 @@ void launch_head_pred(hipStream_t s, const Dims& d, const Work& w, const float* 
 // Block (h' C + c, k) sums the (window, n') pairs [k SKILL_PAIRS, (k + 1) SKILL_PAIRS) in f32 (each thread
 // its pairs in order, then block_sum's fixed tree) into part[k][h' C + c][3]; k_skill_final adds the
 // blocks in order in double onto skill [3][Hf][C] (first pass: overwrites). No atomics: bitwise repeatable.
+// WT (here and in the three score kernels below): every summand times the node weight v = vw[n'] of its target
+// node (smaml_set_score_weights), as (v e) e for the squared terms and v |e|, v var, v CRPS for the others. v == 0
+// skips the element (exactly 0, whatever the target holds); v == 1 gives the unweighted kernel's bits.
 constexpr int SKILL_PAIRS = 1024;
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_skill_part(const float* __restrict__ pred, const float* const* __restrict__ xtab,
                                                    const float* __restrict__ scale, int B, int N, int Hf, int C, int T,
-                                                   int yld, float* __restrict__ part) {
+                                                   int yld, float* __restrict__ part, const float* __restrict__ vw) {
   __shared__ float red[NT / 64];
   const int hc = blockIdx.x, hp = hc / C, c = hc - hp * C;
   const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, B * N);
@@ -1510,9 +1572,17 @@ __global__ __launch_bounds__(NT) void k_skill_part(const float* __restrict__ pre
     const float yl = xs[((int64_t)(T - 1) * N + n) * yld + c];
     const float pv = pred[((int64_t)sm * N * Hf + (int64_t)hp * N + n) * C + c];
     const float e = sc * (pv - y), q = sc * (yl - y);
-    se = fmaf(e, e, se);
-    ae += fabsf(e);
-    pe = fmaf(q, q, pe);
+    if constexpr (WT) {
+      const float v = vw[n];
+      if (v == 0.f) continue;
+      se = fmaf(v * e, e, se);
+      ae += v * fabsf(e);
+      pe = fmaf(v * q, q, pe);
+    } else {
+      se = fmaf(e, e, se);
+      ae += fabsf(e);
+      pe = fmaf(q, q, pe);
+    }
   }
   float* o = part + ((int64_t)blockIdx.y * gridDim.x + hc) * 3;
   const float s0 = block_sum(se, red);
@@ -1538,9 +1608,13 @@ __global__ void k_skill_final(const float* __restrict__ part, int nblk, int HfC,
 int skill_blocks(const Dims& d, int B) { return (B * d.N + SKILL_PAIRS - 1) / SKILL_PAIRS; }
 
 void launch_skill_sums(hipStream_t s, const Dims& d, int B, const float* pred, const float* const* xtab,
-                       const float* scale, float* part, double* skill, bool first) {
+                       const float* scale, float* part, double* skill, bool first, const float* vw) {
   const int nblk = skill_blocks(d, B);
-  k_skill_part<<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part);
+  if (vw)
+    k_skill_part<true><<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part, vw);
+  else
+    k_skill_part<false><<<dim3(d.HfC, nblk), NT, 0, s>>>(pred, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, part,
+                                                        nullptr);
   k_skill_final<<<(3 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, skill, first ? 1 : 0);
 }
 
@@ -1610,9 +1684,10 @@ void launch_rollout_append(hipStream_t s, const RollArgs& a, int j, int gap, boo
 // sums the (origin, node) pairs [k SKILL_PAIRS, (k + 1) SKILL_PAIRS) in f32, k_rollout_skill_final adds the
 // blocks in order in double onto the absolute lead j s + i of skill [3][R s][C]. x = the cycle's block row
 // (gap row included), y = S[o + T + j s + i][n][c], y_last = S[o + T - 1][n][c].
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_rollout_skill_part(RollArgs a, int k0, const float* __restrict__ blk,
                                                            int64_t blk_stride, const float* __restrict__ scale,
-                                                           float* __restrict__ part) {
+                                                           float* __restrict__ part, const float* __restrict__ vw) {
   __shared__ float red[NT / 64];
   const int ic = blockIdx.x, i = ic / a.C, c = ic - i * a.C;
   const int p0 = (int)blockIdx.y * SKILL_PAIRS, p1 = min(p0 + SKILL_PAIRS, a.B * a.N);
@@ -1625,9 +1700,17 @@ __global__ __launch_bounds__(NT) void k_rollout_skill_part(RollArgs a, int k0, c
     const float yl = xs[((int64_t)(a.T - 1) * a.N + n) * a.Cin + c];
     const float x = blk[(int64_t)b * blk_stride + ((int64_t)i * a.N + n) * a.C + c];
     const float e = sc * (x - y), q = sc * (yl - y);
-    se = fmaf(e, e, se);
-    ae += fabsf(e);
-    pe = fmaf(q, q, pe);
+    if constexpr (WT) {
+      const float v = vw[n];
+      if (v == 0.f) continue;
+      se = fmaf(v * e, e, se);
+      ae += v * fabsf(e);
+      pe = fmaf(v * q, q, pe);
+    } else {
+      se = fmaf(e, e, se);
+      ae += fabsf(e);
+      pe = fmaf(q, q, pe);
+    }
   }
   float* o = part + ((int64_t)blockIdx.y * gridDim.x + ic) * 3;
   const float s0 = block_sum(se, red);
@@ -1654,10 +1737,13 @@ __global__ void k_rollout_skill_final(const float* __restrict__ part, int nblk, 
 int rollout_skill_blocks(const Dims& d, int B) { return skill_blocks(d, B); }
 
 void launch_rollout_skill(hipStream_t s, const RollArgs& a, int j, int R, const float* blk, int64_t blk_stride,
-                          const float* scale, float* part, double* skill, bool first) {
+                          const float* scale, float* part, double* skill, bool first, const float* vw) {
   const int sl = a.Hf + 1, sC = sl * a.C;
   const int nblk = (a.B * a.N + SKILL_PAIRS - 1) / SKILL_PAIRS;
-  k_rollout_skill_part<<<dim3(sC, nblk), NT, 0, s>>>(a, j * sl, blk, blk_stride, scale, part);
+  if (vw)
+    k_rollout_skill_part<true><<<dim3(sC, nblk), NT, 0, s>>>(a, j * sl, blk, blk_stride, scale, part, vw);
+  else
+    k_rollout_skill_part<false><<<dim3(sC, nblk), NT, 0, s>>>(a, j * sl, blk, blk_stride, scale, part, nullptr);
   k_rollout_skill_final<<<(3 * sC + 127) / 128, 128, 0, s>>>(part, nblk, sC, j * sC, (int64_t)R * sC, skill,
                                                             first ? 1 : 0);
 }
@@ -1673,11 +1759,12 @@ void launch_rollout_skill(hipStream_t s, const RollArgs& a, int j, int R, const 
 // A thread parks its element's E members in a column of LDS (xs[e][thread]: no per-thread array) and forms
 // everything from there. f32 per block (each thread its pairs in order, then block_sum's fixed tree);
 // k_ens_final adds the blocks in order in double onto scores [4][Hf][C]. No atomics: bitwise repeatable.
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_ens_stats(const float* __restrict__ P, int E, const float* const* __restrict__ xtab,
                                                   const float* __restrict__ scale, int B, int N, int Hf, int C, int T,
                                                   int yld, float* __restrict__ mean, float* __restrict__ spread,
                                                   float* __restrict__ member_pred, int64_t mstride,
-                                                  float* __restrict__ part) {
+                                                  float* __restrict__ part, const float* __restrict__ vw) {
   extern __shared__ float xs[];  // [E][NT]
   __shared__ float red[NT / 64];
   const int hc = blockIdx.x, hp = hc / C, c = hc - hp * C;
@@ -1709,7 +1796,9 @@ __global__ __launch_bounds__(NT) void k_ens_stats(const float* __restrict__ P, i
     const float var = E > 1 ? (float)(ss / (double)(E - 1)) : 0.f;
     if (mean) mean[idx] = mu;
     if (spread) spread[idx] = sqrtf(var);
-    if (part) {
+    float v = 1.f;
+    if constexpr (WT) v = vw[n];
+    if (part && v != 0.f) {
       const float* xw = xtab[sm];
       const float y = xw[((int64_t)(T + 1 + hp) * N + n) * yld + c];
       const float yl = xw[((int64_t)(T - 1) * N + n) * yld + c];
@@ -1721,10 +1810,17 @@ __global__ __launch_bounds__(NT) void k_ens_stats(const float* __restrict__ P, i
       }
       const float crps = ae * invE - pw * invE * invE;
       const float em = sc * (mu - y), q = sc * (yl - y);
-      se = fmaf(em, em, se);
-      sv = fmaf(sc * sc, var, sv);
-      sr = fmaf(sc, crps, sr);
-      pe = fmaf(q, q, pe);
+      if constexpr (WT) {
+        se = fmaf(v * em, em, se);
+        sv = fmaf(sc * sc, v * var, sv);
+        sr = fmaf(sc, v * crps, sr);
+        pe = fmaf(v * q, q, pe);
+      } else {
+        se = fmaf(em, em, se);
+        sv = fmaf(sc * sc, var, sv);
+        sr = fmaf(sc, crps, sr);
+        pe = fmaf(q, q, pe);
+      }
     }
   }
   if (!part) return;
@@ -1753,15 +1849,23 @@ __global__ void k_ens_final(const float* __restrict__ part, int nblk, int HfC, d
 // E = 64 columns are 64 KB of dynamic LDS beside k_ens_stats's static words: above the default per-kernel
 // limit, so the limit is raised on the current device (the caller does it once per context and checks it).
 hipError_t ens_stats_prepare() {
-  return hipFuncSetAttribute((const void*)k_ens_stats, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+  const hipError_t e =
+      hipFuncSetAttribute((const void*)k_ens_stats<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)k_ens_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
 }
 
 void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P, const float* const* xtab,
                       const float* scale, float* mean, float* spread, float* member_pred, int64_t mstride, float* part,
-                      double* scores, bool first) {
+                      double* scores, bool first, const float* vw) {
   const int nblk = skill_blocks(d, B);
-  k_ens_stats<<<dim3(d.HfC, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
-      P, E, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, mean, spread, member_pred, mstride, scores ? part : nullptr);
+  if (vw && scores)
+    k_ens_stats<true><<<dim3(d.HfC, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+        P, E, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, mean, spread, member_pred, mstride, part, vw);
+  else
+    k_ens_stats<false><<<dim3(d.HfC, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+        P, E, xtab, scale, B, d.N, d.Hf, d.C, d.T, d.Cin0, mean, spread, member_pred, mstride, scores ? part : nullptr,
+        nullptr);
   if (scores) k_ens_final<<<(4 * d.HfC + 127) / 128, 128, 0, s>>>(part, nblk, d.HfC, scores, first ? 1 : 0);
 }
 
@@ -1772,11 +1876,12 @@ void launch_ens_stats(hipStream_t s, const Dims& d, int B, int E, const float* P
 // k_ens_stats (double, rounded once) into mean / spread [B][R s][N][C], and with `part` the four f32 block
 // partials against y = S[o + T + q][n][c] and y_last = S[o + T - 1][n][c] (src[b] = S + o_b N Cin). Rows are
 // [N][C] already: no F4 pairing here.
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_rens_stats(const float* __restrict__ X, int64_t estride, int E,
                                                    const float* const* __restrict__ src,
                                                    const float* __restrict__ scale, int B, int N, int Q, int C, int T,
                                                    int yld, float* __restrict__ mean, float* __restrict__ spread,
-                                                   float* __restrict__ part) {
+                                                   float* __restrict__ part, const float* __restrict__ vw) {
   extern __shared__ float xs[];  // [E][NT]
   __shared__ float red[NT / 64];
   const int qc = blockIdx.x, q = qc / C, c = qc - q * C;
@@ -1804,7 +1909,9 @@ __global__ __launch_bounds__(NT) void k_rens_stats(const float* __restrict__ X, 
     const float var = E > 1 ? (float)(ss / (double)(E - 1)) : 0.f;
     if (mean) mean[idx] = mu;
     if (spread) spread[idx] = sqrtf(var);
-    if (part) {
+    float v = 1.f;
+    if constexpr (WT) v = vw[n];
+    if (part && v != 0.f) {
       const float* xw = src[b];
       const float y = xw[((int64_t)(T + q) * N + n) * yld + c];
       const float yl = xw[((int64_t)(T - 1) * N + n) * yld + c];
@@ -1816,10 +1923,17 @@ __global__ __launch_bounds__(NT) void k_rens_stats(const float* __restrict__ X, 
       }
       const float crps = ae * invE - pw * invE * invE;
       const float em = sc * (mu - y), qq = sc * (yl - y);
-      se = fmaf(em, em, se);
-      sv = fmaf(sc * sc, var, sv);
-      sr = fmaf(sc, crps, sr);
-      pe = fmaf(qq, qq, pe);
+      if constexpr (WT) {
+        se = fmaf(v * em, em, se);
+        sv = fmaf(sc * sc, v * var, sv);
+        sr = fmaf(sc, v * crps, sr);
+        pe = fmaf(v * qq, qq, pe);
+      } else {
+        se = fmaf(em, em, se);
+        sv = fmaf(sc * sc, var, sv);
+        sr = fmaf(sc, crps, sr);
+        pe = fmaf(qq, qq, pe);
+      }
     }
   }
   if (!part) return;
@@ -1838,15 +1952,22 @@ __global__ __launch_bounds__(NT) void k_rens_stats(const float* __restrict__ X, 
 
 // (k_ens_final adds the blocks in order in double onto scores [4][Q][C]: the same layout with HfC = Q C)
 hipError_t rens_stats_prepare() {
-  return hipFuncSetAttribute((const void*)k_rens_stats, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+  const hipError_t e =
+      hipFuncSetAttribute((const void*)k_rens_stats<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)k_rens_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * NT * 4);
 }
 
 void launch_rens_stats(hipStream_t s, const Dims& d, int B, int E, int Q, const float* X, int64_t estride,
                        const float* const* src, const float* scale, float* mean, float* spread, float* part,
-                       double* scores, bool first) {
+                       double* scores, bool first, const float* vw) {
   const int nblk = skill_blocks(d, B);
-  k_rens_stats<<<dim3(Q * d.C, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
-      X, estride, E, src, scale, B, d.N, Q, d.C, d.T, d.Cin0, mean, spread, scores ? part : nullptr);
+  if (vw && scores)
+    k_rens_stats<true><<<dim3(Q * d.C, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+        X, estride, E, src, scale, B, d.N, Q, d.C, d.T, d.Cin0, mean, spread, part, vw);
+  else
+    k_rens_stats<false><<<dim3(Q * d.C, nblk), NT, (size_t)E * NT * sizeof(float), s>>>(
+        X, estride, E, src, scale, B, d.N, Q, d.C, d.T, d.Cin0, mean, spread, scores ? part : nullptr, nullptr);
   if (scores) k_ens_final<<<(4 * Q * d.C + 127) / 128, 128, 0, s>>>(part, nblk, Q * d.C, scores, first ? 1 : 0);
 }
 

@@ -375,13 +375,16 @@ void launch_lstm_fwd_dual_wave(hipStream_t s, const Dims& d, const Work& w, int 
 }
 
 // ====================================================================================
+// WT: the weighted loss of k_head_loss (kernels.hip): dpred = dscale (w (p - y)), R dpred = dscale (w R p) -- the
+// loss is quadratic, so that is the whole Hessian term; w == 0 selects +0 for both.
+template <bool WT>
 __global__ __launch_bounds__(NT) void k_head_dual(const float* __restrict__ hT, const float* __restrict__ RhT,
                                                   int64_t zstride, const float* __restrict__ theta,
                                                   const float* __restrict__ U, int64_t tstride, int64_t wo,
                                                   int64_t bo, const float* const* __restrict__ xtab,
                                                   float* __restrict__ dpred, float* __restrict__ Rdpred, int M,
                                                   int H, int HfC, int N, int Hf, int C, int T, int cin0, int B,
-                                                  float dscale) {
+                                                  float dscale, LossW lw) {
   __shared__ float smem[DualStage<CfgNTD>::FLOATS];
   const int z = blockIdx.z;
   const float* th = theta + (int64_t)z * tstride;
@@ -389,6 +392,8 @@ __global__ __launch_bounds__(NT) void k_head_dual(const float* __restrict__ hT, 
   const float* h = hT + (int64_t)z * zstride;
   const float* rh = RhT + (int64_t)z * zstride;
   const int m0 = blockIdx.x * CfgNTD::BM;
+  const float* lwz = nullptr;
+  if constexpr (WT) lwz = lw.w + (int64_t)(lw.zset ? lw.zset[z] : z) * lw.zstride;
   Acc<CfgNTD> ap, at;
   ap.zero();
   at.zero();
@@ -418,8 +423,15 @@ __global__ __launch_bounds__(NT) void k_head_dual(const float* __restrict__ hT, 
         const int hp = rr / N, np = rr - hp * N;
         const float y = xtab[z * B + s][((int64_t)(T + 1 + hp) * N + np) * cin0 + c];
         const int64_t o = ((int64_t)z * M + m) * HfC + cc;
-        dpred[o] = dscale * (p - y);
-        Rdpred[o] = dscale * rp;
+        if constexpr (WT) {
+          const float wv = lwz[((int64_t)hp * N + np) * C + c];
+          const bool on = wv != 0.f;
+          dpred[o] = dscale * (on ? wv * (p - y) : 0.f);
+          Rdpred[o] = dscale * (on ? wv * rp : 0.f);
+        } else {
+          dpred[o] = dscale * (p - y);
+          Rdpred[o] = dscale * rp;
+        }
       }
     }
 }
@@ -436,9 +448,14 @@ void launch_head_dual(hipStream_t s, const Dims& d, const Work& w, const float* 
   const float* hT = head_input(d, w, false, &hz);
   const float* RhT = head_input(d, w, true, &hz);
   dim3 grid((w.M + CfgNTD::BM - 1) / CfgNTD::BM, 1, w.Z);
-  k_head_dual<<<grid, NT, 0, s>>>(hT, RhT, hz, theta, U, tstride, po.wo,
-                                  po.bo, xtab, w.dpred, w.Rdpred, w.M, d.H, d.HfC, d.N, d.Hf, d.C, d.T, d.Cin0, w.B,
-                                  dscale);
+  if (w.lw.w) {
+    k_head_dual<true><<<grid, NT, 0, s>>>(hT, RhT, hz, theta, U, tstride, po.wo, po.bo, xtab, w.dpred, w.Rdpred, w.M,
+                                          d.H, d.HfC, d.N, d.Hf, d.C, d.T, d.Cin0, w.B, dscale, w.lw);
+    count_loss_w(w.lw, 2);
+  } else {
+    k_head_dual<false><<<grid, NT, 0, s>>>(hT, RhT, hz, theta, U, tstride, po.wo, po.bo, xtab, w.dpred, w.Rdpred, w.M,
+                                           d.H, d.HfC, d.N, d.Hf, d.C, d.T, d.Cin0, w.B, dscale, w.lw);
+  }
 }
 
 // ====================================================================================

@@ -33,13 +33,45 @@ def default_windows(t_total: int, window: int, horizon: int, score: bool) -> np.
     return np.arange(n, dtype=np.int32)
 
 
-def skill_reference(pred_norm, features, windows: Sequence[int], dims, scale=None) -> np.ndarray:
+def node_weight_vector(node_weights, N: int):
+    """``node_weights`` as a float64 ``[N]`` vector (finite, >= 0, at least one positive), or None."""
+    if node_weights is None:
+        return None
+    if hasattr(node_weights, "detach"):
+        node_weights = node_weights.detach().cpu()
+    v = np.asarray(node_weights, np.float64).reshape(-1)
+    if v.size != N:
+        raise ValueError(f"node_weights has {v.size} entries, expected {N}")
+    if not np.all(np.isfinite(v)) or np.any(v < 0) or not np.any(v > 0):
+        raise ValueError("node_weights must be finite and >= 0 with at least one positive entry")
+    return v
+
+
+def _node_sum(a, v):
+    """Sum of ``a [K, N, C]`` over its node axis, each node times ``v[n]`` (None: unweighted); a node of weight
+    0 contributes exactly 0 whatever ``a`` holds there (NaN targets of masked nodes)."""
+    if v is None:
+        return a.sum(axis=1)
+    vb = v[None, :, None]
+    with np.errstate(invalid="ignore"):
+        return np.where(vb > 0, a * vb, 0.0).sum(axis=1)
+
+
+def score_count(n: int, N: int, node_weights=None) -> float:
+    """What the score sums of ``n`` windows (origins) divide by: ``n * N``, or ``n * sum(v)`` with node weights."""
+    v = node_weight_vector(node_weights, N)
+    return int(n) * N if v is None else int(n) * float(v.sum())
+
+
+def skill_reference(pred_norm, features, windows: Sequence[int], dims, scale=None, node_weights=None) -> np.ndarray:
     """The three skill sums ``[3, Hf, C]`` (float64; order ``SUMS``) of normalised predictions
     ``pred_norm [nwin, N*Hf, C]`` for the windows ``windows`` of ``features [t_total, N, >= C]``:
     ``sum (s_c (p - y))^2``, ``sum |s_c (p - y)|`` and ``sum (s_c (y_last - y))^2`` over windows and
     nodes, with ``y = features[w+T+1+h', n', c]``, ``y_last = features[w+T-1, n', c]`` and the F4 pairing
-    (module docstring). Pure numpy; needs no GPU."""
+    (module docstring). ``node_weights [N]``: every summand times the weight of its target node ``n'``
+    (``smaml_set_score_weights``; latitude weighting, masks). Pure numpy; needs no GPU."""
     T, Hf, N, C = dims.window_size, dims.forecast_horizon, dims.num_nodes, dims.output_channels
+    v = node_weight_vector(node_weights, N)
     p_all = np.asarray(pred_norm, np.float64).reshape(len(windows), Hf, N, C)  # flat rows seen as [Hf, N]
     f = np.asarray(features)
     s = np.ones(C) if scale is None else np.asarray(scale, np.float64).reshape(C)
@@ -52,9 +84,9 @@ def skill_reference(pred_norm, features, windows: Sequence[int], dims, scale=Non
         y_last = f[w + T - 1, :, :C].astype(np.float64)[None]
         e = (p - y) * s
         q = (y_last - y) * s
-        out[0] += (e * e).sum(axis=1)
-        out[1] += np.abs(e).sum(axis=1)
-        out[2] += (q * q).sum(axis=1)
+        out[0] += _node_sum(e * e, v)
+        out[1] += _node_sum(np.abs(e), v)
+        out[2] += _node_sum(q * q, v)
     return out
 
 
@@ -89,9 +121,27 @@ def _stats(stats, C):
     return mean, std
 
 
+class _score_weights:
+    """Context manager: ``ctx.set_score_weights(v)`` for the call inside, cleared on the way out (a shared
+    context is left as found). None: nothing to do."""
+
+    def __init__(self, ctx, node_weights, N):
+        self.ctx, self.v = ctx, node_weight_vector(node_weights, N)
+
+    def __enter__(self):
+        if self.v is not None:
+            self.ctx.set_score_weights(self.v)
+        return self
+
+    def __exit__(self, *exc):
+        if self.v is not None:
+            self.ctx.set_score_weights(None)
+        return False
+
+
 def forecast(model, features, edge_index, stats=None, windows=None, batch: int = 64, score: bool = True,
              return_pred: bool = True, ctx=None,
-             edge_weight=None) -> ForecastResult:
+             edge_weight=None, node_weights=None) -> ForecastResult:
     """``model``: the drop-in ``HybridSTGCN_LSTM`` (its weights, prepared as ``evaluate_regional``
     prepares it); ``features``: the region's normalised ``[T_total, N, 24]`` stream (a tensor on the HIP
     device or a numpy array); ``stats``: ``{"mean": [..], "std": [..]}`` of the adaptation checkpoint
@@ -99,7 +149,10 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
     run in passes of ``batch``; consecutive windows share their GCN features and input projections.
     ``score=False`` forecasts only (windows may then reach the end of the stream); ``return_pred=False``
     keeps the predictions on the device pass by pass and returns the metrics alone. ``ctx``: a
-    ``_capi.Context`` of the model's shape to run on (default: the model's own cached one)."""
+    ``_capi.Context`` of the model's shape to run on (default: the model's own cached one). ``node_weights
+    [N]``: weights of the score sums per target node (``loss.latitude_weights`` for an area-weighted RMSE; 0
+    masks a node, whose targets may then be NaN); the metrics divide by ``nwin * sum(v)``. The context's score
+    weights are cleared again before returning."""
     import torch
 
     from . import _capi
@@ -134,7 +187,7 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
     mean, std = _stats(stats, C)
     pred = torch.empty(w.size, N * Hf, C, device=dev) if return_pred else None
     sums = torch.empty(3, Hf, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad():
+    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
         ctx.forecast(_capi.stream_ptr(torch), theta, w, batch, scale=std if score else None, pred=pred, skill=sums)
         out = None
         if pred is not None:
@@ -143,7 +196,7 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
             out = (pred * scale_t + shift_t).view(w.size, Hf, N, C).cpu().numpy()
     if not score:
         return ForecastResult(out, None, None, None, None, int(w.size), w)
-    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), int(w.size) * N)
+    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), score_count(w.size, N, node_weights))
     return ForecastResult(out, rmse, mae, prmse, skill, int(w.size), w)
 
 
@@ -224,11 +277,13 @@ def rollout_reference(forward, features, origins: Sequence[int], dims, cycles: i
     return out
 
 
-def rollout_skill_reference(traj, features, origins: Sequence[int], dims, scale=None) -> np.ndarray:
+def rollout_skill_reference(traj, features, origins: Sequence[int], dims, scale=None, node_weights=None) -> np.ndarray:
     """The three sums ``[3, R s, C]`` (float64; order ``SUMS``) of a normalised trajectory ``traj
     [norig, R s, N, C]`` per absolute lead ``k`` and variable, over origins and nodes: every row (gap rows
-    included) against ``y = features[o + T + k]``, and the persistence ``y_last = features[o + T - 1]``."""
+    included) against ``y = features[o + T + k]``, and the persistence ``y_last = features[o + T - 1]``.
+    ``node_weights``: as ``skill_reference``."""
     T, N, C = dims.window_size, dims.num_nodes, dims.output_channels
+    v = node_weight_vector(node_weights, N)
     x = np.asarray(traj, np.float64)
     x = x.reshape(len(origins), -1, N, C)
     K = x.shape[1]
@@ -243,9 +298,9 @@ def rollout_skill_reference(traj, features, origins: Sequence[int], dims, scale=
         y_last = f[o + T - 1, :, :C].astype(np.float64)[None]
         e = (xi - y) * sc
         q = (y_last - y) * sc
-        out[0] += (e * e).sum(axis=1)
-        out[1] += np.abs(e).sum(axis=1)
-        out[2] += (q * q).sum(axis=1)
+        out[0] += _node_sum(e * e, v)
+        out[1] += _node_sum(np.abs(e), v)
+        out[2] += _node_sum(q * q, v)
     return out
 
 
@@ -265,14 +320,14 @@ class RolloutResult:
 
 def rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, gap="midpoint", batch: int = 32,
             score: bool = True, ctx=None,
-            edge_weight=None) -> RolloutResult:
+            edge_weight=None, node_weights=None) -> RolloutResult:
     """Autoregressive forecast of ``cycles`` x ``(Hf + 1)`` steps from every origin (``smaml_forecast_rollout``):
     each cycle's prediction is fed back as the weather channels of the next window, the exogenous channels
     come from ``features`` (use ``extend_stream`` to forecast past the last observation, with ``score=False``).
     Arguments as ``forecast``; ``origins`` defaults to ``rollout_origins``; ``gap``: "midpoint" or
     "persistence" fills the row between a window and its first target. Returns the trajectory in physical
     units and, with ``score``, RMSE / MAE / persistence RMSE / skill per absolute lead and variable (count per
-    lead: ``norig * N``)."""
+    lead: ``norig * N``, or ``norig * sum(v)`` with ``node_weights``, which weigh the sums as in ``forecast``)."""
     import torch
 
     from . import _capi
@@ -310,7 +365,7 @@ def rollout(model, features, edge_index, stats=None, origins=None, cycles: int =
     mean, std = _stats(stats, C)
     traj = torch.empty(o.size, R, s, N, C, device=dev)
     sums = torch.empty(3, R * s, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad():
+    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
         ctx.forecast_rollout(_capi.stream_ptr(torch), theta, o, batch, R, g, scale=std if score else None, traj=traj,
                              skill=sums)
         scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
@@ -318,7 +373,7 @@ def rollout(model, features, edge_index, stats=None, origins=None, cycles: int =
         out = (traj * scale_t + shift_t).view(o.size, R * s, N, C).cpu().numpy()
     if not score:
         return RolloutResult(out, is_gap, None, None, None, None, int(o.size), o, R, gname)
-    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), int(o.size) * N)
+    rmse, mae, prmse, skill = skill_metrics(sums.cpu().numpy(), score_count(o.size, N, node_weights))
     return RolloutResult(out, is_gap, rmse, mae, prmse, skill, int(o.size), o, R, gname)
 
 
@@ -326,14 +381,16 @@ def rollout(model, features, edge_index, stats=None, origins=None, cycles: int =
 ENSEMBLE_SUMS =("mean_sse", "variance", "crps", "persistence_sse")  # order of smaml_forecast_ensemble's scores
 
 
-def ensemble_reference(member_pred, features, windows: Sequence[int], dims, scale=None):
+def ensemble_reference(member_pred, features, windows: Sequence[int], dims, scale=None, node_weights=None):
     """``(mean, spread, sums)`` in float64 of the members ``member_pred [E, nwin, N*Hf, C]`` (normalised):
     ``mean`` / ``spread [nwin, N*Hf, C]`` -- the member mean and the unbiased standard deviation about it
     (0 at E = 1) -- and ``sums [4, Hf, C]`` (order ``ENSEMBLE_SUMS``) over windows and nodes with
     ``skill_reference``'s pairing, targets and scale: ``sum (s (mu - y))^2``, ``sum s^2 sigma^2``,
     ``sum s CRPS`` with ``CRPS = (1/E) sum_i |x_i - y| - (1/(2 E^2)) sum_ij |x_i - x_j|`` and the persistence
-    ``sum (s (y_last - y))^2``. Pure numpy; needs no GPU."""
+    ``sum (s (y_last - y))^2``. ``node_weights``: as ``skill_reference`` (the sums only; mean and spread are
+    not affected). Pure numpy; needs no GPU."""
     T, Hf, N, C = dims.window_size, dims.forecast_horizon, dims.num_nodes, dims.output_channels
+    v = node_weight_vector(node_weights, N)
     x = np.asarray(member_pred, np.float64)
     E, nwin = x.shape[0], len(windows)
     x = x.reshape(E, nwin, N * Hf, C)
@@ -351,10 +408,10 @@ def ensemble_reference(member_pred, features, windows: Sequence[int], dims, scal
         y_last = f[w + T - 1, :, :C].astype(np.float64)[None]
         xi = xv[:, i]
         crps = np.abs(xi - y).sum(axis=0) / E - np.abs(xi[:, None] - xi[None, :]).sum(axis=(0, 1)) / (2.0 * E * E)
-        sums[0] += (((mv[i] - y) * s) ** 2).sum(axis=1)
-        sums[1] += (vv[i] * s * s).sum(axis=1)
-        sums[2] += (crps * s).sum(axis=1)
-        sums[3] += (((y_last - y) * s) ** 2).sum(axis=1)
+        sums[0] += _node_sum(((mv[i] - y) * s) ** 2, v)
+        sums[1] += _node_sum(vv[i] * s * s, v)
+        sums[2] += _node_sum(crps * s, v)
+        sums[3] += _node_sum(((y_last - y) * s) ** 2, v)
     return mean, np.sqrt(var), sums
 
 
@@ -394,14 +451,15 @@ class EnsembleResult:
 def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16, p_gcn=None, p_lstm=None,
                       seed=None, windows=None, batch: int = 32, score: bool = True, return_members: bool = False,
                       ctx=None,
-                      edge_weight=None) -> EnsembleResult:
+                      edge_weight=None, node_weights=None) -> EnsembleResult:
     """MC-dropout ensemble of ``forecast``: ``members`` stochastic forwards per window, member ``e`` under the
     library's masks of ``(seed, step e)`` (what ``model.train()``'s forward under ``no_grad`` computes), in
     lockstep over the member axis. ``p_gcn`` / ``p_lstm`` default to the model's own dropout rates
     (``base_stgcn.dropout.p``, ``dropout.p``), ``seed`` to ``draw_dropout_seed()``. Returns the ensemble mean
     (``mean * std + mean_stat``) and spread (``spread * std``) in physical units, optionally every member, and
     with ``score`` the metrics of ``ensemble_metrics``; ``score=False`` forecasts only (windows may then reach
-    the end of the stream). Other arguments as ``forecast``.
+    the end of the stream). Other arguments as ``forecast`` (``node_weights`` included: the four sums are
+    weighted, the metrics divide by ``nwin * sum(v)``).
 
     Cost: with ``p_gcn == 0`` the GCN features, layer 0's projection and LSTM layer 0 are computed once for all
     members (16 members measured 0.69 x 16 deterministic ``forecast`` runs at N = 441). With ``p_gcn > 0`` --
@@ -448,7 +506,7 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
     spread = torch.empty(w.size, N * Hf, C, device=dev)
     mem = torch.empty(E, w.size, N * Hf, C, device=dev) if return_members else None
     sums = torch.empty(4, Hf, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad():
+    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
         ctx.forecast_ensemble(_capi.stream_ptr(torch), theta, w, batch, E, p_gcn, p_lstm, seed,
                               scale=std if score else None, mean=mean, spread=spread, member_pred=mem, scores=sums)
         scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
@@ -459,7 +517,7 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
     if not score:
         return EnsembleResult(mean_o, spread_o, mem_o, None, None, None, None, None, int(w.size), E, w, seed, p_gcn,
                               p_lstm)
-    rmse, rms, ratio, crps, prmse = ensemble_metrics(sums.cpu().numpy(), int(w.size) * N, E)
+    rmse, rms, ratio, crps, prmse = ensemble_metrics(sums.cpu().numpy(), score_count(w.size, N, node_weights), E)
     return EnsembleResult(mean_o, spread_o, mem_o, rmse, rms, ratio, crps, prmse, int(w.size), E, w, seed, p_gcn, p_lstm)
 
 
@@ -467,15 +525,17 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
 # Every MC-dropout member feeds its OWN forecast back in: how the spread grows with lead time, and whether it
 # keeps pace with the error of the ensemble mean. Cycle j of member e runs under the masks of step 64 j + e, so
 # cycle 0 is ``ensemble_forecast``'s member e and a member does not depend on E, R or the pass size.
-def ensemble_rollout_reference(member_traj, features, origins: Sequence[int], dims, scale=None):
+def ensemble_rollout_reference(member_traj, features, origins: Sequence[int], dims, scale=None, node_weights=None):
     """``(mean, spread, sums)`` in float64 of the member trajectories ``member_traj [E, norig, R s, N, C]``
     (normalised; any shape that reshapes to it): ``mean`` / ``spread [norig, R s, N, C]`` -- the member mean and
     the unbiased standard deviation about it (0 at E = 1) -- and ``sums [4, R s, C]`` (order ``ENSEMBLE_SUMS``) per
     absolute lead ``k`` and variable over origins and nodes, every row (gap rows included) against
     ``y = features[o + T + k]`` and the persistence ``y_last = features[o + T - 1]``: ``sum (s (mu - y))^2``,
     ``sum s^2 sigma^2``, ``sum s CRPS`` with ``CRPS = (1/E) sum_i |x_i - y| - (1/(2 E^2)) sum_ij |x_i - x_j|``,
-    ``sum (s (y_last - y))^2``. Rows are ``[N, C]`` already: no F4 pairing. Pure numpy; needs no GPU."""
+    ``sum (s (y_last - y))^2``. Rows are ``[N, C]`` already: no F4 pairing. ``node_weights``: as
+    ``skill_reference``. Pure numpy; needs no GPU."""
     T, N, C = dims.window_size, dims.num_nodes, dims.output_channels
+    v = node_weight_vector(node_weights, N)
     x = np.asarray(member_traj, np.float64)
     E, norig = x.shape[0], len(origins)
     x = x.reshape(E, norig, -1, N, C)
@@ -493,10 +553,10 @@ def ensemble_rollout_reference(member_traj, features, origins: Sequence[int], di
         y_last = f[o + T - 1, :, :C].astype(np.float64)[None]
         xi = x[:, i]
         crps = np.abs(xi - y).sum(axis=0) / E - np.abs(xi[:, None] - xi[None, :]).sum(axis=(0, 1)) / (2.0 * E * E)
-        sums[0] += (((mean[i] - y) * s) ** 2).sum(axis=1)
-        sums[1] += (var[i] * s * s).sum(axis=1)
-        sums[2] += (crps * s).sum(axis=1)
-        sums[3] += (((y_last - y) * s) ** 2).sum(axis=1)
+        sums[0] += _node_sum(((mean[i] - y) * s) ** 2, v)
+        sums[1] += _node_sum(var[i] * s * s, v)
+        sums[2] += _node_sum(crps * s, v)
+        sums[3] += _node_sum(((y_last - y) * s) ** 2, v)
     return mean, np.sqrt(var), sums
 
 
@@ -537,14 +597,14 @@ class EnsembleRolloutResult:
 def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycles: int = 3, members: int = 16,
                      p_gcn=None, p_lstm=None, seed=None, gap="midpoint", batch: int = 32, score: bool = True,
                      return_members: bool = False, ctx=None,
-                     edge_weight=None) -> EnsembleRolloutResult:
+                     edge_weight=None, node_weights=None) -> EnsembleRolloutResult:
     """``rollout`` for an MC-dropout ensemble (``smaml_forecast_rollout_ensemble``): each of the ``members`` feeds
     its own forecast back in for ``cycles`` x ``(Hf + 1)`` steps, member ``e`` of cycle ``j`` under the library's
     masks of ``(seed, step 64 j + e)``. Defaults as ``ensemble_forecast`` (the model's own dropout rates,
     ``draw_dropout_seed()``) and ``rollout`` (``rollout_origins``; ``extend_stream`` with ``score=False`` to forecast
     past the last observation). Returns the ensemble mean and spread along the trajectory in physical units,
     optionally every member, and with ``score`` the metrics of ``ensemble_rollout_metrics`` per absolute lead and
-    variable (count per lead: ``norig * N``).
+    variable (count per lead: ``norig * N``, or ``norig * sum(v)`` with ``node_weights``, as in ``forecast``).
 
     Cost: with ``p_gcn == 0`` the observed rows' GCN features and projection are computed once per pass for all
     members and cycle 0 shares LSTM layer 0; ``p_gcn > 0`` recomputes every member's whole window each cycle on
@@ -593,7 +653,7 @@ def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycl
     spread = torch.empty(o.size, R, s, N, C, device=dev)
     mem = torch.empty(E, o.size, R, s, N, C, device=dev) if return_members else None
     sums = torch.empty(4, R * s, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad():
+    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
         ctx.forecast_rollout_ensemble(_capi.stream_ptr(torch), theta, o, batch, R, E, p_gcn, p_lstm, seed, gap=g,
                                       scale=std if score else None, member_traj=mem, mean=mean, spread=spread,
                                       scores=sums)
@@ -604,5 +664,6 @@ def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycl
         mem_o = (mem * scale_t + shift_t).view(E, o.size, R * s, N, C).cpu().numpy() if mem is not None else None
     if not score:
         return EnsembleRolloutResult(mean_o, spread_o, mem_o, is_gap, None, None, None, None, None, None, *tail)
-    rmse, rms, ratio, crps, prmse, skill = ensemble_rollout_metrics(sums.cpu().numpy(), int(o.size) * N)
+    rmse, rms, ratio, crps, prmse, skill = ensemble_rollout_metrics(sums.cpu().numpy(),
+                                                                    score_count(o.size, N, node_weights))
     return EnsembleRolloutResult(mean_o, spread_o, mem_o, is_gap, rmse, rms, ratio, crps, prmse, skill, *tail)

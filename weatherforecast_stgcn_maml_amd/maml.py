@@ -159,14 +159,25 @@ class MetaLearner:
         self.pg = process_group
         self.tasks: List[torch.Tensor] = []
         self._groups = []
+        self._loss_w_live = False  # the context holds a table this learner uploaded
+        self._loss_w = None  # [nsets, Hf*N, C] float32 of set_tasks(loss_weights=), nsets = 1 or the task count
         # HIP events around the per-meta-step all-reduce (bench: the collective's exposed time)
         self.comm_timing = False
         self._comm_ev = []
 
     # tasks are [t_total, N, 24] float32 feature streams resident in HBM
-    def set_tasks(self, features: Sequence, task_ids: Optional[Sequence[int]] = None):
+    def set_tasks(self, features: Sequence, task_ids: Optional[Sequence[int]] = None, loss_weights=None):
         """``task_ids``: global ids of these tasks (dropout mask keys; default 0..n-1). An empty
-        list is allowed (a rank with no task still joins the all-reduce with zeros)."""
+        list is allowed (a rank with no task still joins the all-reduce with zeros).
+        ``loss_weights``: one table ``[Hf*N, C]`` for every task or one per task ``[n, Hf*N, C]``
+        (``loss.make_loss_weights``); the inner-loop and query losses are then ``mean W (pred - y)^2``
+        (``smaml_set_loss_weights``). None clears the context's table."""
+        self._loss_w = None
+        if loss_weights is not None and len(features):
+            self._loss_w = _capi._loss_table(self.dims, loss_weights)
+            if self._loss_w.shape[0] not in (1, len(features)):
+                raise ValueError(f"{self._loss_w.shape[0]} loss weight tables for {len(features)} tasks "
+                                 "(one table, or one per task)")
         feats = []
         for f in features:
             t = f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f))
@@ -175,6 +186,7 @@ class MetaLearner:
         self.task_ids = np.asarray(task_ids if task_ids is not None else np.arange(len(feats)), np.int32)
         if not feats:
             self._groups = []
+            self._upload_loss_weights(None)
             return
         tg = self.task_group
         if tg == "auto":
@@ -183,8 +195,20 @@ class MetaLearner:
         G = min(tg or len(feats), len(feats))
         self._groups = [(z0, feats[z0:z0 + G]) for z0 in range(0, len(feats), G)]
         self.ctx.set_tasks(self._groups[0][1])
+        # (one table, or a single group: uploaded once; per-task tables of several groups: before each group's pass)
+        self._upload_loss_weights(self._loss_w if self._loss_w is None or len(self._groups) == 1 or
+                                  self._loss_w.shape[0] == 1 else self._loss_w[:len(self._groups[0][1])])
         self.ctx.reserve(G, self.cfg.batch)
         self._mg_part = torch.zeros_like(self.meta_grad) if len(self._groups) > 1 else None
+
+    def _upload_loss_weights(self, w):
+        """The context's loss table: ``w``, or cleared -- which touches the context only if this learner set one."""
+        if w is not None:
+            self.ctx.set_loss_weights(w)
+            self._loss_w_live = True
+        elif self._loss_w_live:
+            self.ctx.set_loss_weights(None)
+            self._loss_w_live = False
 
     def default_windows(self) -> np.ndarray:
         """The window table meta_step uses without an explicit one: support samples
@@ -227,6 +251,8 @@ class MetaLearner:
                 ng = torch.empty(max(K, 1), n, device=self.device)
                 self.ctx.set_tasks(grp)
                 self.ctx.set_task_ids(self.task_ids[z0:z0 + n])
+                if self._loss_w is not None and self._loss_w.shape[0] > 1:
+                    self._upload_loss_weights(self._loss_w[z0:z0 + n])
                 mg = (self.meta_grad if gi == 0 else self._mg_part) if cfg.order >= 1 else None
                 self.ctx.meta_step(stream, self.theta, cfg.order, K, cfg.batch, windows[:, z0:z0 + n],
                                    cfg.inner_lr, cfg.max_norm, cfg.query_loss_scale, meta_grad=mg,

@@ -45,10 +45,19 @@ class OuterLR:
         return self.sched.state_dict()
 
 
+def _task_tables(loss_weights, idx, n):
+    """The loss weights of the tasks ``idx`` drawn for a meta-step: one table serves every task; a stack of ``n``
+    tables (one per task of the whole pool) is indexed as the tasks are."""
+    if loss_weights is None:
+        return None
+    w = np.asarray(loss_weights, np.float32)
+    return w if w.ndim == 2 else w[np.asarray(idx)] if w.shape[0] == n else w
+
+
 def meta_train(dims: ModelDims, features: Sequence, edge_index, gcn_full: dict, theta: dict, cfg: MamlConfig,
                epochs: int = NUM_EPOCHS, batch_tasks: int = BATCH_SIZE, koppen_state: Optional[dict] = None,
                log_csv: Optional[str] = None, ckpt_dir: Optional[str] = None, seed: int = SEED,
-               device: str = "cuda", verbose: bool = True, dropout=(0.0, 0.0)):
+               device: str = "cuda", verbose: bool = True, dropout=(0.0, 0.0), loss_weights=None):
     """Returns (learner, history). ``gcn_full`` holds every non-trainable hybrid tensor
     (conv params + the unused ``base_stgcn.output_layer``) for the checkpoint. ``dropout`` =
     (STGCN dropout_rate, lstm_dropout): the reference trains with (0.2, 0.2); the default (0, 0)
@@ -78,7 +87,7 @@ def meta_train(dims: ModelDims, features: Sequence, edge_index, gcn_full: dict, 
             idx = rng.choice(n, batch_tasks, replace=False)
         else:
             idx = np.arange(n)
-        ml.set_tasks([feats[i] for i in idx], task_ids=idx)
+        ml.set_tasks([feats[i] for i in idx], task_ids=idx, loss_weights=_task_tables(loss_weights, idx, n))
         res = ml.meta_step(lr=sched.lr)
         loss = res.meta_loss
         if len(task_losses) < n:
