@@ -285,6 +285,23 @@ def test_short_window():
             assert st["shared_rows"] == 11 * 3 and st["member_rows"] == 2 * 11 * 2 * 3
 
 
+def test_sixty_four_members():
+    """More than 32 members: k_rens_stats needs its dynamic-LDS limit raised (64 KB at E = 64, its largest
+    footprint). Member 0 teacher-forced against the oracle (test 1's bound), the statistics against the reference
+    on the GPU's own members (test 2's bound)."""
+    c = case(CONFIG1)
+    ctx = c.context()
+    mt, mean, spread, scores = run(c, ctx, [0, 1], 2, 2, 64, 0.0, 0.2)
+    for x in (mt, mean, spread, scores):
+        assert not np.any(x == SENT) and np.all(np.isfinite(x))
+    check_teacher_forced(c, c.feats, mt[:1], [0, 1], 2, 1, 0.0, 0.2)
+    assert rel(mt[0, :, 1], mt[63, :, 1]) > 1e-3  # the last member is another draw
+    m_ref, s_ref, q_ref = forecast.ensemble_rollout_reference(mt, c.feats, [0, 1], c.d, SCALE)
+    r = (relmax(mean.reshape(m_ref.shape), m_ref), relmax(spread.reshape(s_ref.shape), s_ref), relmax(scores, q_ref))
+    print(f"64 members: mean {r[0]:.3g}, spread {r[1]:.3g}, scores {r[2]:.3g} (max rel)")
+    assert max(r) <= 1e-5
+
+
 # 7 ---------------------------------------------------------------------------------------------------
 def test_nan_guard_and_state_isolation():
     c = case(CONFIG1)

@@ -520,14 +520,19 @@ class Context:
         out["windows_filled_per_step"] = filled.value
         return out
 
+    def _list_and_scale(self, entries, scale):
+        """The forecast calls' window or origin list as a flat int32 array and ``scale`` (or None) as float32 [C]."""
+        e = np.ascontiguousarray(entries, dtype=np.int32).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+        if sc is not None and sc.size != self.dims.output_channels:
+            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        return e, sc
+
     def forecast(self, stream, theta, windows, batch, task=0, scale=None, pred=None, skill=None):
         """Rolling forecast of ``windows`` (starts into task ``task``'s stream) in passes of ``batch``:
         ``pred`` [nwin, N*Hf, C] float32 and / or ``skill`` [3, Hf, C] float64 device tensors
         (smaml_forecast; ``scale`` = per-variable factors of the skill sums, host, [C])."""
-        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
-        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-        if sc is not None and sc.size != self.dims.output_channels:
-            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        w, sc = self._list_and_scale(windows, scale)
         check(self._L.smaml_forecast(self._h, stream, ptr(theta), int(task), w.ctypes.data_as(PI32), w.size, int(batch),
                                      sc.ctypes.data_as(PF32) if sc is not None else None,
                                      ptr(pred) if pred is not None else None,
@@ -539,10 +544,7 @@ class Context:
         ``e`` under the masks of ``(seed, step e)``. Device tensors, each optional: ``mean`` / ``spread``
         [nwin, N*Hf, C], ``member_pred`` [members, nwin, N*Hf, C] float32, ``scores`` [4, Hf, C] float64
         (``forecast.ENSEMBLE_SUMS``; ``scale`` = their per-variable factors, host, [C])."""
-        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
-        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-        if sc is not None and sc.size != self.dims.output_channels:
-            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        w, sc = self._list_and_scale(windows, scale)
         opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
         check(self._L.smaml_forecast_ensemble(
             self._h, stream, ptr(theta), int(task), w.ctypes.data_as(PI32), w.size, int(batch), int(members),
@@ -555,10 +557,7 @@ class Context:
         stream) in passes of ``batch`` (smaml_forecast_rollout): ``traj`` [norig, cycles, Hf + 1, N, C] float32
         and / or ``skill`` [3, cycles * (Hf + 1), C] float64 device tensors; ``gap`` 1 = midpoint, 0 =
         persistence (``ROLLOUT_GAPS``); ``scale`` = per-variable factors of the skill sums, host, [C]."""
-        o = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
-        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-        if sc is not None and sc.size != self.dims.output_channels:
-            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        o, sc = self._list_and_scale(origins, scale)
         check(self._L.smaml_forecast_rollout(self._h, stream, ptr(theta), int(task), o.ctypes.data_as(PI32), o.size,
                                              int(batch), int(cycles), int(gap),
                                              sc.ctypes.data_as(PF32) if sc is not None else None,
@@ -582,10 +581,7 @@ class Context:
         ``spread`` [norig, cycles, Hf + 1, N, C] float32, ``scores`` [4, cycles * (Hf + 1), C] float64
         (``forecast.ENSEMBLE_SUMS``; ``scale`` = their per-variable factors, host, [C]); ``gap`` as
         ``forecast_rollout``."""
-        o = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
-        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-        if sc is not None and sc.size != self.dims.output_channels:
-            raise ValueError(f"scale has {sc.size} entries, expected {self.dims.output_channels}")
+        o, sc = self._list_and_scale(origins, scale)
         opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
         check(self._L.smaml_forecast_rollout_ensemble(
             self._h, stream, ptr(theta), int(task), o.ctypes.data_as(PI32), o.size, int(batch), int(cycles), int(gap),

@@ -1467,241 +1467,6 @@ int run_backward_dual(smaml_ctx* c, hipStream_t s, const float* theta, const flo
   return SMAML_OK;
 }
 
-// ---- smaml_forecast: inference passes on buffers of their own ---------------------------------------
-// Whether a forecast pass of consecutive windows stores its GCN features compact (the distinct stream
-// rows only, XgDedup order). The forecast's only reader of F is layer 0's gate step -- every diagonal on
-// the big tiles (k_lstm_fwd_infer has no other form) and nothing differentiates -- so unlike f_compact_ok
-// neither the weight-gradient path nor the tile choice enters: it takes the GCN and the projection once
-// per distinct row (the options of the training step) and the table they go through.
-bool forecast_compact_ok(const smaml_ctx* c, bool consec, int B, bool have_xg) {
-  const Knobs& kn = c->kn;
-  return consec && B > 1 && kn.f_compact && kn.gcn_dedup && kn.xg_dedup && have_xg;
-}
-
-// One pass of B windows of one stream (xt: their device pointer table; consec: w[b] = w[0] + b): GCN, layer
-// 0's projection per distinct stream row (consecutive passes), the inference wavefront, the head into
-// pred_out [B][N*Hf][C] and, with skill, the pass's sums added onto it. Runs in c->w (the caller saves
-// and restores the training state's) on the forecast's buffers only.
-int forecast_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
-                  float* pred_out, const float* scale_dev, double* skill, bool first) {
-  const Dims& d = c->d;
-  const Knobs& kn = c->kn;
-  const int M = B * d.N;
-  const bool dedup_gcn = consec && kn.gcn_dedup && B > 1;
-  const bool fused = gcn_mlp_supported(d) && kn.gcn_fused;
-  const bool want_xg = consec && kn.xg_dedup && B > 1;
-  const int64_t xrows = xg_dedup_rows(B, d.T, d.N);
-  const bool have_xg = want_xg && c->fc_xg.grow(xrows * 4 * d.H * 4) == hipSuccess;
-  const bool compact = forecast_compact_ok(c, consec, B, have_xg);
-  // GCN scratch rows: the t = 0 blocks on the fused path; else every row, or (per-layer dedup) each task's
-  // B + T - 1 stream rows
-  const int64_t grows = fused       ? (int64_t)M
-                        : dedup_gcn ? std::max<int64_t>((int64_t)(B + d.T - 1) * d.N, M)
-                                    : (int64_t)d.T * M;
-  const int64_t ring = infer_ring_floats(d, 1, M);
-  if (c->fc_ring.grow(2 * ring * 4) != hipSuccess ||
-      c->fc_F.grow((compact ? xrows : (int64_t)d.T * M) * d.Hc * 4) != hipSuccess ||
-      grow_all<HipAlloc>({{&c->fc_gcnA, grows * d.Hc * 4}, {&c->fc_gcnB, grows * d.Hc * 4}}) != hipSuccess ||
-      (!pred_out && c->fc_pred.grow((int64_t)M * d.HfC * 4) != hipSuccess) ||
-      (skill && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 3 * 4) != hipSuccess))
-    return fail(SMAML_ENOMEM, "hipMalloc of the forecast buffers failed (batch " + std::to_string(B) + ")");
-  Work w{};
-  w.Z = 1;
-  w.B = B;
-  w.M = M;
-  w.F = c->fc_F.as<float>();
-  w.gcnA = c->fc_gcnA.as<float>();
-  w.gcnB = c->fc_gcnB.as<float>();
-  w.vcount = c->vcount;
-  w.kn = kn;
-  c->w = w;
-  TRY(run_gcn(c, s, xt, consec ? xt : nullptr, compact ? 1 : 0));
-  TRY(prep_gate_images(c, s, theta, 0));
-  Work& cw = c->w;
-  if (have_xg) {
-    XgDedup xd{};
-    xd.zstride = xrows * 4 * d.H;
-    xd.N = d.N;
-    cw.xgd = xd;  // (zstride read by the launcher)
-    float* dst = c->fc_xg.as<float>();
-    const bool img = cw.gimg.th && cw.gimg_src == theta;
-    TIMED(c, s, C_XG, 2.0 * xrows * 4 * d.H * c->po.lay[0].cin,
-          launch_xg_dedup(s, d, cw, theta, 0, c->po, img ? cw.gimg.th : nullptr, cw.gimg.tstride, cw.gimg.off[0][0],
-                          dst));
-    xd.xg = dst;
-    xd.src = theta;
-    cw.xgd = xd;
-  }
-  float* ringH = c->fc_ring.as<float>();
-  float* ringC = ringH + ring;
-  for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
-    FwdWave wv{};
-    double fl = fwd_wave(d, cw, c->po, diag, 0, false, wv);
-    if (have_xg)  // (the projection's flops are counted in C_XG)
-      for (int q = 0; q < wv.n; ++q)
-        if (wv.l[q] == 0) fl -= 2.0 * M * 4 * d.H * wv.lo[q].cin;
-    TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer(s, d, cw, diag, theta, 0, c->po, ringH, ringC));
-  }
-  float* pred = pred_out ? pred_out : c->fc_pred.as<float>();
-  TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
-        launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
-  if (skill)
-    TIMED(c, s, C_MISC, 0,
-          launch_skill_sums(s, d, B, pred, xt, scale_dev, c->fc_part.as<float>(), skill, first, score_weights(c)));
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
-}
-
-// ---- smaml_forecast_ensemble: MC-dropout members in lockstep ------------------------------------------
-// Members of one launch set for a pass of M rows: `want` (option ens_group; 0 = all), else the largest
-// group whose rings -- and, with GCN dropout, per-member features -- stay within ENS_GROUP_BUDGET.
-constexpr int64_t ENS_GROUP_BUDGET = 2ll << 30;
-int ens_group_size(const Dims& d, int M, int E, bool per_member_F, int want) {
-  if (want > 0) return std::min(want, E);
-  if (want == 0) return E;
-  const int64_t per = 2 * infer_ring_floats(d, 1, M) * 4 + (per_member_F ? (int64_t)d.T * M * d.Hc * 4 : 0);
-  return (int)std::max<int64_t>(1, std::min<int64_t>(E, ENS_GROUP_BUDGET / per));
-}
-
-struct EnsArgs {
-  int E = 0;
-  float p_gcn = 0.f, p_lstm = 0.f;
-  uint32_t seed = 0;
-  int64_t done = 0, nwin = 0;  // this pass's first window in the call's list, and the list's length
-};
-
-// One pass of B windows for all E members (forecast_pass's counterpart). p_gcn == 0: the GCN features and
-// layer 0's projection once for all members (forecast_pass's own dedup and compact layout), layer 0 of the
-// LSTM once (option ens_share), layers >= 1 with grid z = member. p_gcn > 0: each member's GCN on the
-// per-layer launchers, masked in place after conv1..conv3 (kind 1), into its own F. The members'
-// predictions go to c->ens_pred [E][B][N*Hf][C], from which k_ens_stats forms every output.
-int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
-                  const EnsArgs& a, const float* scale_dev, float* mean, float* spread, float* member_pred,
-                  double* scores) {
-  const Dims& d = c->d;
-  const Knobs& kn = c->kn;
-  const int M = B * d.N, E = a.E;
-  const bool shared = a.p_gcn == 0.f;
-  const int G = ens_group_size(d, M, E, !shared, c->ens_group);
-  const bool dedup_gcn = shared && consec && kn.gcn_dedup && B > 1;
-  const bool fused = shared && gcn_mlp_supported(d) && kn.gcn_fused;
-  const bool want_xg = shared && consec && kn.xg_dedup && B > 1;
-  const int64_t xrows = xg_dedup_rows(B, d.T, d.N);
-  const bool have_xg = want_xg && c->fc_xg.grow(xrows * 4 * d.H * 4) == hipSuccess;
-  const bool compact = shared && forecast_compact_ok(c, consec, B, have_xg);
-  const int64_t grows = fused       ? (int64_t)M
-                        : dedup_gcn ? std::max<int64_t>((int64_t)(B + d.T - 1) * d.N, M)
-                                    : (int64_t)d.T * M;
-  const int64_t ring = infer_ring_floats(d, G, M);
-  const int64_t fslab = (int64_t)d.T * M * d.Hc;  // floats of one member's own features
-  if (c->ens_ring.grow(2 * ring * 4) != hipSuccess ||
-      c->fc_F.grow((shared ? (compact ? xrows * d.Hc : fslab) : G * fslab) * 4) != hipSuccess ||
-      grow_all<HipAlloc>({{&c->fc_gcnA, grows * d.Hc * 4}, {&c->fc_gcnB, grows * d.Hc * 4}}) != hipSuccess ||
-      c->ens_pred.grow((int64_t)E * M * d.HfC * 4) != hipSuccess ||
-      (scores && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 4 * 4) != hipSuccess))
-    return fail(SMAML_ENOMEM, "hipMalloc of the ensemble buffers failed (batch " + std::to_string(B) + ", " +
-                                  std::to_string(G) + " members at a time)");
-  Work w{};
-  w.Z = 1;
-  w.B = B;
-  w.M = M;
-  w.F = c->fc_F.as<float>();
-  w.gcnA = c->fc_gcnA.as<float>();
-  w.gcnB = c->fc_gcnB.as<float>();
-  w.vcount = c->vcount;
-  w.kn = kn;
-  c->w = w;
-  if (shared) TRY(run_gcn(c, s, xt, consec ? xt : nullptr, compact ? 1 : 0));
-  TRY(prep_gate_images(c, s, theta, 0));
-  Work& cw = c->w;
-  if (have_xg) {
-    XgDedup xd{};
-    xd.zstride = xrows * 4 * d.H;
-    xd.N = d.N;
-    cw.xgd = xd;  // (zstride read by the launcher)
-    float* dst = c->fc_xg.as<float>();
-    const bool img = cw.gimg.th && cw.gimg_src == theta;
-    TIMED(c, s, C_XG, 2.0 * xrows * 4 * d.H * c->po.lay[0].cin,
-          launch_xg_dedup(s, d, cw, theta, 0, c->po, img ? cw.gimg.th : nullptr, cw.gimg.tstride, cw.gimg.off[0][0],
-                          dst));
-    xd.xg = dst;
-    xd.src = theta;
-    cw.xgd = xd;
-  }
-  EnsDrop ed{};
-  ed.seed = a.seed;
-  ed.thr = (uint32_t)std::lround((double)a.p_lstm * 16777216.0);
-  ed.sc = 1.f / (1.f - a.p_lstm);
-  ed.row0 = a.done * d.N;
-  ed.Mtot = a.nwin * d.N;
-  // (a one-layer LSTM has no layer above to read a shared layer 0: its layer 0 is the top layer, whose h_T
-  // every member masks and hands to the head itself)
-  ed.share0 = shared && c->ens_share && d.L > 1 ? 1 : 0;
-  const uint32_t thr_gcn = (uint32_t)std::lround((double)a.p_gcn * 16777216.0);
-  float* ringH = c->ens_ring.as<float>();
-  float* ringC = ringH + ring;
-  float* P = c->ens_pred.as<float>();
-  for (int e0 = 0; e0 < E; e0 += G) {
-    const int g = std::min(G, E - e0);
-    if (!shared) {
-      // STGCN features of member e0 + z under its own masks: conv k over the T N-row samples (the t = 0 rows
-      // with the graph), then the kind-1 mask of (step e, layer k) at the batch-wide element index
-      // ((done + b) T N + row) Hc + channel = base + the buffer's own linear index
-      const int rps = d.T * d.N;
-      const GraphView gv = graph_view(c);
-      float* bufs[2] = {cw.gcnA, cw.gcnB};
-      for (int z = 0; z < g; ++z) {
-        const float* src = nullptr;
-        for (int k = 0; k < 4; ++k) {
-          const bool last = k == 3;
-          float* dst = last ? cw.F + (int64_t)z * fslab : bufs[k & 1];
-          TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
-                launch_gcn_layer(s, d, k, B, B, k == 0 ? xt : nullptr, src, dst, last, true, c->gcn + c->go.w[k],
-                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N, nullptr));
-          if (!last)
-            TIMED(c, s, C_GCN, 0,
-                  launch_ens_dropout(s, dst, (int64_t)B * rps * d.Hc, 1, a.seed, 1, e0 + z, k, thr_gcn,
-                                     1.f / (1.f - a.p_gcn), (uint64_t)a.done * rps * d.Hc));
-          src = dst;
-        }
-      }
-    }
-    ed.e0 = e0;
-    for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
-      FwdWave wv{};
-      double fl = 0.0;
-      fwd_wave(d, cw, c->po, diag, 0, false, wv);
-      for (int q = 0; q < wv.n; ++q) {  // layer 0 once when shared, without its projection when tabled
-        const double k1 = (wv.l[q] == 0 && have_xg ? 0 : wv.lo[q].cin) + (wv.t[q] > 0 ? d.H : 0);
-        fl += 2.0 * (wv.l[q] == 0 && ed.share0 ? 1 : g) * M * 4 * d.H * k1;
-      }
-      TIMED(c, s, C_FWD, fl,
-            launch_lstm_fwd_infer_drop(s, d, cw, diag, theta, c->po, ringH, ringC, g, shared ? 0 : fslab, ed));
-    }
-    // (the rings are laid out for g members: [L][2][g][M][H])
-    float* hT = ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * g * M * d.H;
-    if (ed.thr)
-      TIMED(c, s, C_HEAD, 0,
-            launch_ens_dropout(s, hT, (int64_t)M * d.H, g, a.seed, 3, e0, 0, ed.thr, ed.sc, (uint64_t)ed.row0 * d.H));
-    Work hw = cw;
-    hw.Z = g;
-    TIMED(c, s, C_HEAD, 2.0 * g * M * d.HfC * d.H,
-          launch_head_pred(s, d, hw, hT, (int64_t)M * d.H, theta, 0, c->po, P + (int64_t)e0 * M * d.HfC));
-  }
-  if (E > 32 && !c->ens_lds_set) {
-    const hipError_t st = ens_stats_prepare();
-    if (st != hipSuccess)
-      return fail(SMAML_EHIP, std::string("smaml_forecast_ensemble: raising k_ens_stats's dynamic LDS limit to 64 KB "
-                                          "(more than 32 members) failed: ") + hipGetErrorString(st));
-    c->ens_lds_set = true;
-  }
-  TIMED(c, s, C_MISC, 0,
-        launch_ens_stats(s, d, B, E, P, xt, scale_dev, mean, spread, member_pred, a.nwin * d.N * d.HfC,
-                         c->fc_part.as<float>(), scores, a.done == 0, scores ? score_weights(c) : nullptr));
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
-}
-
 bool graph_set(const smaml_ctx* c) { return c->graph_form != 0; }
 
 int require_ready(smaml_ctx* c) {
@@ -1832,6 +1597,723 @@ int gcn_backward_chain(smaml_ctx* c, hipStream_t s, const float* x0, float* cons
     }
     std::swap(g, gn);
   }
+  return SMAML_OK;
+}
+
+// ---- the forecast family: smaml_forecast, _ensemble, _rollout, _rollout_ensemble --------------------------
+// Inference on buffers of their own. Every entry point is forecast_check, its buffers and pointer table, then
+// forecast_run over its pass function; every pass function is a sequence of the stages below.
+
+// One call as its entry point received it.
+struct ForecastCall {
+  const char* name = nullptr;       // the entry point, for messages
+  const char* no_output = nullptr;  // what the message says of a call whose output pointers are all NULL
+  bool any_output = false;
+  const float* theta = nullptr;
+  const int32_t* list = nullptr;    // window starts; rollouts: origins
+  int n = 0, batch = 0, task = 0;
+  bool score = false;               // skill / scores asked for
+  const float* scale_host = nullptr;
+  bool rollout = false;
+  int cycles = 0, gap = 0;
+  bool ens = false;
+  int members = 0;
+  float p_gcn = 0.f, p_lstm = 0.f;
+  uint32_t seed = 0;
+};
+
+constexpr int RENS_MAX_CYCLES = 1024;  // drop_site gives `step` 16 bits (step << 8 below kind << 24): 64 j + e < 2^16
+
+// rows of an origin's private sequence: its window, then the Hf + 1 rows every cycle but the last appends
+int64_t roll_seq_rows(const Dims& d, int R) { return d.T + (int64_t)(R - 1) * (d.Hf + 1); }
+
+// The argument checks (they need no context and run without a device too), the state checks, then every window
+// or origin against its stream: its input rows must fit and, when scoring, so must the last targets, Hf + 1
+// rows on. Last the device.
+int forecast_check(smaml_ctx* c, const ForecastCall& a) {
+  const std::string fn = std::string(a.name) + ": ";
+  if (!a.any_output) return fail(SMAML_EINVAL, fn + a.no_output);
+  if (a.n <= 0 || a.batch <= 0 || !a.list)
+    return fail(SMAML_EINVAL, fn + (a.rollout ? "norig" : "nwin") + " and batch must be positive");
+  if (a.ens && (a.members < 1 || a.members > 64))
+    return fail(SMAML_EINVAL, fn + "members must be in 1..64, got " + std::to_string(a.members));
+  if (a.rollout && !a.ens && a.cycles <= 0) return fail(SMAML_EINVAL, fn + "cycles must be positive");
+  if (a.rollout && a.ens && (a.cycles < 1 || a.cycles > RENS_MAX_CYCLES))
+    return fail(SMAML_EINVAL, fn + "cycles must be in 1.." + std::to_string(RENS_MAX_CYCLES) +
+                                  " (the mask site's step 64 j + e has 16 bits), got " + std::to_string(a.cycles));
+  if (a.ens && (!(a.p_gcn >= 0.f && a.p_gcn < 1.f) || !(a.p_lstm >= 0.f && a.p_lstm < 1.f)))
+    return fail(SMAML_EINVAL, fn + "dropout probabilities must be in [0, 1)");
+  if (a.rollout && a.gap != 0 && a.gap != 1)
+    return fail(SMAML_EINVAL, fn + "gap must be 0 (persistence) or 1 (midpoint), got " + std::to_string(a.gap));
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, a.name));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  if (!a.theta || !aligned16(a.theta)) return fail(SMAML_EINVAL, fn + "theta must be a 16-byte aligned device pointer");
+  if (a.task < 0 || a.task >= (int)c->feats.size()) return fail(SMAML_EINVAL, fn + "task out of range");
+  const Dims& d = c->d;
+  if ((int64_t)d.T * std::min(a.batch, a.n) * d.N * 4 * d.H >= (a.rollout ? 1ll << 30 : 1ll << 31))
+    return fail(SMAML_EINVAL,
+                std::string("batch too large: T*B*N*4H must stay below ") + (a.rollout ? "2^30" : "2^31"));
+  const int64_t tt = c->t_total[a.task];
+  const int64_t need_in = a.rollout ? roll_seq_rows(d, a.cycles) : d.T, need_sc = need_in + d.Hf + 1;
+  for (int i = 0; i < a.n; ++i) {
+    const int64_t o = a.list[i];
+    const bool fits = o >= 0 && o + need_in <= tt;
+    if (fits && !(a.score && o + need_sc > tt)) continue;
+    std::string m = fn + (a.rollout ? "origin " : "window ") + std::to_string(i) + " (start " + std::to_string(o);
+    if (a.rollout)
+      m += (fits ? ") has no targets for " : ") does not fit ") + std::to_string(a.cycles) + " cycles in";
+    else
+      m += fits ? ") has no targets in" : ") does not fit";
+    return fail(SMAML_EINVAL, m + " the stream of " + std::to_string(tt) + " steps");
+  }
+  TRY(ensure_device(c));
+  TRY(check_device_error(c));
+  return SMAML_OK;
+}
+
+// The pointer table of a call over windows: entry i = window i's first stream row.
+std::vector<const float*> window_ptrs(const smaml_ctx* c, const ForecastCall& a) {
+  std::vector<const float*> ptrs(a.n);
+  for (int i = 0; i < a.n; ++i) ptrs[i] = c->feats[a.task] + (int64_t)a.list[i] * c->d.N * c->d.Cin0;
+  return ptrs;
+}
+
+// whether a pass's B windows start at consecutive stream rows (w[b] = w[0] + b; a single window does not count)
+bool windows_consec(const int32_t* w, int B) {
+  bool consec = B > 1;
+  for (int b = 1; b < B && consec; ++b) consec = w[b] == w[0] + b;
+  return consec;
+}
+
+// Uploads the scale (when scoring with one) and the pointer table, then body(done, B, scale_dev) per pass of at
+// most a.batch entries. The training state stays as it is: the family never touches the arena, and the
+// workspace view (with the activations a pending smaml_backward / smaml_lstm_backward will consume) is put
+// back on every path.
+template <class Body>
+int forecast_run(smaml_ctx* c, hipStream_t s, const ForecastCall& a, const std::vector<const float*>& ptrs, Body body) {
+  const Work saved = c->w;
+  const int act = c->act_B;
+  auto run = [&]() -> int {
+    const float* scale_dev = nullptr;
+    if (a.score && a.scale_host) {
+      HIP_TRY(c->fc_scale.grow((int64_t)c->d.C * 4));
+      TRY(c->stage.upload(s, c->fc_scale.ptr, a.scale_host, (int64_t)c->d.C * 4));
+      scale_dev = c->fc_scale.as<float>();
+    }
+    TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
+    for (int64_t done = 0; done < a.n; done += a.batch)
+      TRY(body(done, (int)std::min<int64_t>(a.batch, a.n - done), scale_dev));
+    return SMAML_OK;
+  };
+  const int rc = run();
+  c->w = saved;
+  c->act_B = act;
+  return rc;
+}
+
+// -- stages --
+// c->w for a pass of B windows or origins, on the forecast's buffers
+void forecast_work(smaml_ctx* c, int B) {
+  Work w{};
+  w.Z = 1;
+  w.B = B;
+  w.M = B * c->d.N;
+  w.F = c->fc_F.as<float>();
+  w.gcnA = c->fc_gcnA.as<float>();
+  w.gcnB = c->fc_gcnB.as<float>();
+  w.vcount = c->vcount;
+  w.kn = c->kn;
+  c->w = w;
+}
+
+// Whether a forecast pass of consecutive windows stores its GCN features compact (the distinct stream
+// rows only, XgDedup order). The forecast's only reader of F is layer 0's gate step -- every diagonal on
+// the big tiles (k_lstm_fwd_infer has no other form) and nothing differentiates -- so unlike f_compact_ok
+// neither the weight-gradient path nor the tile choice enters: it takes the GCN and the projection once
+// per distinct row (the options of the training step) and the table they go through.
+bool forecast_compact_ok(const smaml_ctx* c, bool consec, int B, bool have_xg) {
+  const Knobs& kn = c->kn;
+  return consec && B > 1 && kn.f_compact && kn.gcn_dedup && kn.xg_dedup && have_xg;
+}
+
+// How a pass of B windows shares its GCN features: layer 0's projection per distinct stream row (have_xg;
+// grows fc_xg), F compact, and the rows of F (frows) and of the GCN scratch (grows: the t = 0 blocks on the
+// fused path; else every row, or (per-layer dedup) each task's B + T - 1 stream rows).
+struct FeatPlan {
+  bool have_xg = false, compact = false;
+  int64_t xrows = 0, frows = 0, grows = 0;
+};
+
+FeatPlan feat_plan(smaml_ctx* c, int B, bool consec) {
+  const Dims& d = c->d;
+  const Knobs& kn = c->kn;
+  const int64_t M = (int64_t)B * d.N;
+  FeatPlan f;
+  f.xrows = xg_dedup_rows(B, d.T, d.N);
+  f.have_xg = consec && kn.xg_dedup && B > 1 && c->fc_xg.grow(f.xrows * 4 * d.H * 4) == hipSuccess;
+  f.compact = forecast_compact_ok(c, consec, B, f.have_xg);
+  f.frows = f.compact ? f.xrows : d.T * M;
+  f.grows = gcn_mlp_supported(d) && kn.gcn_fused    ? M
+            : consec && kn.gcn_dedup && B > 1       ? std::max<int64_t>((int64_t)(B + d.T - 1) * d.N, M)
+                                                    : d.T * M;
+  return f;
+}
+
+// The features every row of the pass reads, once: the GCN into c->w.F, the gate images and, with have_xg, layer
+// 0's projection of the distinct stream rows into fc_xg (c->w.xgd).
+int shared_features(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, bool consec,
+                    const FeatPlan& f) {
+  const Dims& d = c->d;
+  TRY(run_gcn(c, s, xt, consec ? xt : nullptr, f.compact ? 1 : 0));
+  TRY(prep_gate_images(c, s, theta, 0));
+  Work& cw = c->w;
+  if (f.have_xg) {
+    XgDedup xd{};
+    xd.zstride = f.xrows * 4 * d.H;
+    xd.N = d.N;
+    cw.xgd = xd;  // (zstride read by the launcher)
+    float* dst = c->fc_xg.as<float>();
+    const bool img = cw.gimg.th && cw.gimg_src == theta;
+    TIMED(c, s, C_XG, 2.0 * f.xrows * 4 * d.H * c->po.lay[0].cin,
+          launch_xg_dedup(s, d, cw, theta, 0, c->po, img ? cw.gimg.th : nullptr, cw.gimg.tstride, cw.gimg.off[0][0],
+                          dst));
+    xd.xg = dst;
+    xd.src = theta;
+    cw.xgd = xd;
+  }
+  return SMAML_OK;
+}
+
+// The inference wavefront of c->w on rings [L][2][1][M][H] and the head into pred [M][HfC]. (Layer 0's
+// projection, when c->w.xgd tables it, is counted in C_XG.)
+void infer_waves(smaml_ctx* c, hipStream_t s, const float* theta, float* ringH, float* ringC, float* pred) {
+  const Dims& d = c->d;
+  const Work& cw = c->w;
+  const int M = cw.M;
+  for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+    FwdWave wv{};
+    double fl = fwd_wave(d, cw, c->po, diag, 0, false, wv);
+    if (cw.xgd.xg)
+      for (int q = 0; q < wv.n; ++q)
+        if (wv.l[q] == 0) fl -= 2.0 * M * 4 * d.H * wv.lo[q].cin;
+    TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer(s, d, cw, diag, theta, 0, c->po, ringH, ringC));
+  }
+  TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
+        launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
+}
+
+// The same for g members in lockstep (grid z) under the masks of ed, member z's features fz floats past c->w.F
+// (0: shared): the wavefront on rings [L][2][g][M][H], the kind-3 mask of every member's h_T, the head into
+// pred [g][M][HfC]. Layer 0 counts once when ed.share0, and without its projection when tabled.
+void infer_waves_drop(smaml_ctx* c, hipStream_t s, const float* theta, float* ringH, float* ringC, int g, int64_t fz,
+                      const EnsDrop& ed, float* pred) {
+  const Dims& d = c->d;
+  const Work& cw = c->w;
+  const int M = cw.M;
+  for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
+    FwdWave wv{};
+    double fl = 0.0;
+    fwd_wave(d, cw, c->po, diag, 0, false, wv);
+    for (int q = 0; q < wv.n; ++q) {
+      const double k1 = (wv.l[q] == 0 && cw.xgd.xg ? 0 : wv.lo[q].cin) + (wv.t[q] > 0 ? d.H : 0);
+      fl += 2.0 * (wv.l[q] == 0 && ed.share0 ? 1 : g) * M * 4 * d.H * k1;
+    }
+    TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer_drop(s, d, cw, diag, theta, c->po, ringH, ringC, g, fz, ed));
+  }
+  float* hT = const_cast<float*>(infer_ring_hT(d, ringH, g, M));
+  if (ed.thr)
+    TIMED(c, s, C_HEAD, 0,
+          launch_ens_dropout(s, hT, (int64_t)M * d.H, g, ed.seed, 3, ed.e0, 0, ed.thr, ed.sc, (uint64_t)ed.row0 * d.H));
+  Work hw = cw;
+  hw.Z = g;
+  TIMED(c, s, C_HEAD, 2.0 * g * M * d.HfC * d.H, launch_head_pred(s, d, hw, hT, (int64_t)M * d.H, theta, 0, c->po, pred));
+}
+
+// The masks of a call's LSTM dropout for the pass whose first entry is `done` of the call's n
+EnsDrop ens_drop(const Dims& d, const ForecastCall& a, int64_t done) {
+  EnsDrop ed{};
+  ed.seed = a.seed;
+  ed.thr = (uint32_t)std::lround((double)a.p_lstm * 16777216.0);
+  ed.sc = 1.f / (1.f - a.p_lstm);
+  ed.row0 = done * d.N;
+  ed.Mtot = (int64_t)a.n * d.N;
+  return ed;
+}
+
+// One member's STGCN features under its own masks, into dst [T][M][Hc]: conv k over the B samples of T N rows
+// that start at tab[b] (the t = 0 rows with the graph), then the kind-1 mask of (step, layer k) at the call-wide
+// element index base + the buffer's own linear index.
+void member_gcn_masked(smaml_ctx* c, hipStream_t s, const float* const* tab, const ForecastCall& a, int step,
+                       uint64_t base, float* dst) {
+  const Dims& d = c->d;
+  const Work& cw = c->w;
+  const int B = cw.B, rps = d.T * d.N;
+  const GraphView gv = graph_view(c);
+  const uint32_t thr_gcn = (uint32_t)std::lround((double)a.p_gcn * 16777216.0);
+  float* bufs[2] = {cw.gcnA, cw.gcnB};
+  const float* from = nullptr;
+  for (int k = 0; k < 4; ++k) {
+    const bool last = k == 3;
+    float* to = last ? dst : bufs[k & 1];
+    TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
+          launch_gcn_layer(s, d, k, B, B, k == 0 ? tab : nullptr, from, to, last, true, c->gcn + c->go.w[k],
+                           c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N, nullptr));
+    if (!last)
+      TIMED(c, s, C_GCN, 0,
+            launch_ens_dropout(s, to, (int64_t)B * rps * d.Hc, 1, a.seed, 1, step, k, thr_gcn, 1.f / (1.f - a.p_gcn),
+                               base));
+    from = to;
+  }
+}
+
+// The statistics kernel of more than 32 members needs its dynamic-LDS limit raised, once per context.
+int raise_stats_lds(bool* set, int E, hipError_t (*prepare)(), const char* entry, const char* kernel) {
+  if (E <= 32 || *set) return SMAML_OK;
+  const hipError_t st = prepare();
+  if (st != hipSuccess)
+    return fail(SMAML_EHIP, std::string(entry) + ": raising " + kernel + "'s dynamic LDS limit to 64 KB (more than 32 "
+                                "members) failed: " + hipGetErrorString(st));
+  *set = true;
+  return SMAML_OK;
+}
+
+// The per-layer GCN chain over `ns` samples of rps rows each that start at tab[i] (the first ell_rows of each
+// aggregate over the graph), time-major into dst over all ns samples; in chunks of samples whose buffers stay
+// below 2^30 bytes (the layer kernel's loaders index in 32 bits). drop_rps: launch_gcn_layer's.
+void gcn_chain(smaml_ctx* c, hipStream_t s, const float* const* tab, int ns, int rps, int ell_rows, int drop_rps,
+               float* dst) {
+  const Dims& d = c->d;
+  const GraphView gv = graph_view(c);
+  float* bufs[2] = {c->w.gcnA, c->w.gcnB};
+  const int cs = (int)std::max<int64_t>(1, (1ll << 28) / ((int64_t)rps * d.Hc));
+  for (int s0 = 0; s0 < ns; s0 += cs) {
+    const int n = std::min(cs, ns - s0);
+    const float* from = nullptr;
+    for (int k = 0; k < 4; ++k) {
+      const bool last = k == 3;
+      float* to = last ? dst + (int64_t)s0 * d.N * d.Hc : bufs[k & 1];
+      TIMED(c, s, C_GCN, 2.0 * n * rps * c->go.cin[k] * d.Hc,
+            launch_gcn_layer(s, d, k, n, ns, k == 0 ? tab + s0 : nullptr, from, to, last, true, c->gcn + c->go.w[k],
+                             c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, ell_rows, nullptr, drop_rps));
+      from = to;
+    }
+  }
+}
+
+// -- stages of the two rollouts --
+// First private row whose features cycle j computes: with reuse only the rows the previous cycle appended
+// that the window's steps t >= 1 read (all of them when T > s; when T <= s the window holds fewer rows than a
+// cycle appends), else every row t >= 1 of the window. The run ends at row j s + T - 1.
+int roll_run_first(int j, int T, int sl, bool reuse) {
+  if (j == 0 || !reuse) return j * sl + 1;
+  return std::max(j * sl + 1, (j - 1) * sl + T);
+}
+
+// What a rollout call fixes for all its passes. G members of a group run side by side (1: the deterministic
+// rollout). The uploaded table: src[norig] (origin rows); ensemble: obs[norig] (the same one step on); then one
+// set per pass size -- tabB[0] = Bmax and, where the ensemble's last pass is smaller, tabB[1] behind it -- of per
+// cycle win[G * B], run[G * B], entry z * B + b. The deterministic rollout reads its tail pass from the one set.
+struct RollPlan {
+  int Bmax = 0, Btail = 0, S = 0, G = 1;
+  bool reuse = true, fused = false;
+  int64_t tab_src = 0, tab_obs = 0, tab_cyc[2] = {0, 0};
+  int tabB[2] = {0, 0};
+};
+
+RollPlan roll_plan(const smaml_ctx* c, const ForecastCall& a) {
+  RollPlan p{};
+  p.Bmax = std::min(a.batch, a.n);
+  p.Btail = a.ens && a.n % a.batch ? a.n % a.batch : p.Bmax;
+  p.S = c->d.T;
+  p.reuse = c->roll_reuse != 0;
+  p.fused = gcn_mlp_supported(c->d) && c->kn.gcn_fused;
+  return p;
+}
+
+// Builds the table described at RollPlan over the private sequences seq [G * Bmax][seq_rows][N][Cin0] and
+// records where its parts start.
+std::vector<const float*> roll_table(const smaml_ctx* c, const ForecastCall& a, const float* seq, RollPlan& p) {
+  const Dims& d = c->d;
+  const int sl = d.Hf + 1, R = a.cycles, nset = p.Btail != p.Bmax ? 2 : 1;
+  const int64_t rowf = (int64_t)d.N * d.Cin0, seq_rows = roll_seq_rows(d, R), head = (a.ens ? 2 : 1) * (int64_t)a.n;
+  std::vector<const float*> ptrs((size_t)head + (size_t)R * 2 * p.G * (p.Bmax + (nset == 2 ? p.Btail : 0)));
+  for (int i = 0; i < a.n; ++i) {
+    ptrs[i] = c->feats[a.task] + (int64_t)a.list[i] * rowf;
+    if (a.ens) ptrs[(size_t)a.n + i] = ptrs[i] + rowf;
+  }
+  p.tab_src = 0;
+  p.tab_obs = a.n;
+  // without a set of its own a smaller last pass reads set 0, at set 0's stride (entry z * Bmax + b, b < B)
+  p.tab_cyc[0] = p.tab_cyc[1] = head;
+  p.tabB[0] = p.tabB[1] = p.Bmax;
+  int64_t at = head;
+  for (int k = 0; k < nset; ++k) {
+    if (k == 1) {
+      p.tab_cyc[1] = at;
+      p.tabB[1] = p.Btail;
+    }
+    const int GB = p.G * p.tabB[k];
+    for (int j = 0; j < R; ++j)
+      for (int zb = 0; zb < GB; ++zb) {
+        const float* sb = seq + (int64_t)zb * seq_rows * rowf;
+        ptrs[(size_t)(at + ((int64_t)j * 2) * GB + zb)] = sb + (int64_t)j * sl * rowf;
+        ptrs[(size_t)(at + ((int64_t)j * 2 + 1) * GB + zb)] = sb + (int64_t)roll_run_first(j, d.T, sl, p.reuse) * rowf;
+      }
+    at += (int64_t)R * 2 * GB;
+  }
+  return ptrs;
+}
+
+// cycle j's window (win) and run tables of a pass of B origins
+int roll_tabs(const smaml_ctx* c, const RollPlan& p, int j, int B, const float* const** win, const float* const** run) {
+  const int k = B == p.Bmax ? 0 : 1;
+  const int64_t GB = (int64_t)p.G * p.tabB[k];
+  TRY(xtab_at(c, p.tab_cyc[k] + (int64_t)j * 2 * GB, win));
+  TRY(xtab_at(c, p.tab_cyc[k] + ((int64_t)j * 2 + 1) * GB, run));
+  return SMAML_OK;
+}
+
+// What a rollout pass's stages share: the GCN weight offsets, layer 0's gate image and the sequence addressing
+struct RollSetup {
+  GcnWOff wo;
+  const char* gimg = nullptr;
+  int64_t gimg_off = 0;
+  RollArgs ra;
+};
+
+// c->w and the gate images for a pass of B origins with rows from src, the fused stack's weight image (wsplit),
+// and the addressing of the private sequences seq.
+int roll_setup(smaml_ctx* c, hipStream_t s, const float* theta, int B, int R, float* seq, const float* const* src,
+               bool wsplit, RollSetup* rs) {
+  const Dims& d = c->d;
+  forecast_work(c, B);
+  TRY(prep_gate_images(c, s, theta, 0));
+  const Work& cw = c->w;
+  rs->gimg = cw.gimg.th && cw.gimg_src == theta ? cw.gimg.th : nullptr;
+  rs->gimg_off = cw.gimg.off[0][0];
+  for (int k = 0; k < 4; ++k) {
+    rs->wo.w[k] = c->go.w[k];
+    rs->wo.b[k] = c->go.b[k];
+  }
+  if (wsplit) TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, rs->wo, c->gcn_wimg.as<char>()));
+  RollArgs& ra = rs->ra;
+  ra = RollArgs{};
+  ra.seq = seq;
+  ra.seq_rows = (int)roll_seq_rows(d, R);
+  ra.seq_stride = (int64_t)ra.seq_rows * d.N * d.Cin0;
+  ra.src = src;
+  ra.B = B;
+  ra.N = d.N;
+  ra.Cin = d.Cin0;
+  ra.C = d.C;
+  ra.Hf = d.Hf;
+  ra.T = d.T;
+  return SMAML_OK;
+}
+
+// The four position-independent convs of `nrun` rows t >= 1 of each of ns samples (from tab[i]), time-major
+// into F: the fused stack, or the per-layer chain
+void gcn_rows(smaml_ctx* c, hipStream_t s, const RollSetup& rs, bool fused, const float* const* tab, int ns, int nrun,
+              int drop_rps, float* F) {
+  const Dims& d = c->d;
+  if (fused)
+    TIMED(c, s, C_GCN, 2.0 * ns * nrun * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+          launch_gcn_mlp_run(s, d, ns, nrun, tab, c->gcn, rs.wo, c->gcn_wimg.as<char>(), F));
+  else
+    gcn_chain(c, s, tab, ns, nrun * d.N, 0, drop_rps, F);
+}
+
+// Layer 0's projection of plain rows F [rows][Hc] into out [rows][4H], in launches whose output stays below
+// 2^32 bytes (k_xg_dedup's stores index in 32 bits). blocks (optional) += the N-row blocks projected.
+void xg_rows(smaml_ctx* c, hipStream_t s, const float* theta, const RollSetup& rs, const float* F, int64_t rows,
+             float* out, int64_t* blocks) {
+  const Dims& d = c->d;
+  const int64_t cr = ((1ll << 30) / (4 * d.H) - 1) / 256 * 256;
+  for (int64_t r = 0; r < rows; r += cr) {
+    const int64_t n = std::min(cr, rows - r);
+    TIMED(c, s, C_XG, 2.0 * n * 4 * d.H * c->po.lay[0].cin,
+          launch_xg_rows(s, d, c->w, F + r * d.Hc, n, theta, c->po, rs.gimg, rs.gimg_off, out + r * 4 * d.H));
+  }
+  if (blocks) *blocks += rows / d.N;
+}
+
+// The projection of a run of nrun steps (F time-major, gM rows per step) into the slots of the ring table xg
+// [S][gM][4H] from row r0 on: a run that wraps the table takes two launches
+void xg_run_slots(smaml_ctx* c, hipStream_t s, const float* theta, const RollSetup& rs, const float* F, int r0,
+                  int nrun, int S, int64_t gM, float* xg, int64_t* blocks) {
+  const Dims& d = c->d;
+  for (int tau = 0; tau < nrun;) {
+    const int sl0 = (r0 + tau) % S, len = std::min(nrun - tau, S - sl0);
+    xg_rows(c, s, theta, rs, F + (int64_t)tau * gM * d.Hc, (int64_t)len * gM, xg + (int64_t)sl0 * gM * 4 * d.H, blocks);
+    tau += len;
+  }
+}
+
+// -- the pass functions --
+// One pass of B windows of one stream (xt: their device pointer table; consec: w[b] = w[0] + b): GCN, layer
+// 0's projection per distinct stream row (consecutive passes), the inference wavefront, the head into
+// pred_out [B][N*Hf][C] and, with skill, the pass's sums added onto it.
+int forecast_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
+                  float* pred_out, const float* scale_dev, double* skill, bool first) {
+  const Dims& d = c->d;
+  const int M = B * d.N;
+  const FeatPlan f = feat_plan(c, B, consec);
+  const int64_t ring = infer_ring_floats(d, 1, M);
+  if (c->fc_ring.grow(2 * ring * 4) != hipSuccess || c->fc_F.grow(f.frows * d.Hc * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, f.grows * d.Hc * 4}, {&c->fc_gcnB, f.grows * d.Hc * 4}}) != hipSuccess ||
+      (!pred_out && c->fc_pred.grow((int64_t)M * d.HfC * 4) != hipSuccess) ||
+      (skill && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 3 * 4) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the forecast buffers failed (batch " + std::to_string(B) + ")");
+  forecast_work(c, B);
+  TRY(shared_features(c, s, theta, xt, consec, f));
+  float* ringH = c->fc_ring.as<float>();
+  float* pred = pred_out ? pred_out : c->fc_pred.as<float>();
+  infer_waves(c, s, theta, ringH, ringH + ring, pred);
+  if (skill)
+    TIMED(c, s, C_MISC, 0,
+          launch_skill_sums(s, d, B, pred, xt, scale_dev, c->fc_part.as<float>(), skill, first, score_weights(c)));
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+// Members of one launch set for a pass of M rows: `want` (option ens_group; 0 = all), else the largest
+// group whose rings -- and, with GCN dropout, per-member features -- stay within ENS_GROUP_BUDGET.
+constexpr int64_t ENS_GROUP_BUDGET = 2ll << 30;
+int ens_group_size(const Dims& d, int M, int E, bool per_member_F, int want) {
+  if (want > 0) return std::min(want, E);
+  if (want == 0) return E;
+  const int64_t per = 2 * infer_ring_floats(d, 1, M) * 4 + (per_member_F ? (int64_t)d.T * M * d.Hc * 4 : 0);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(E, ENS_GROUP_BUDGET / per));
+}
+
+// One pass of B windows (first of them `done` in the call's list) for all E members. p_gcn == 0: the shared
+// features of forecast_pass once for all members, layer 0 of the LSTM once (option ens_share), layers >= 1 with
+// grid z = member. p_gcn > 0: each member's masked GCN into its own F. The members' predictions go to
+// c->ens_pred [E][B][N*Hf][C], from which k_ens_stats forms every output.
+int ensemble_pass(smaml_ctx* c, hipStream_t s, const float* theta, const float* const* xt, int B, bool consec,
+                  const ForecastCall& a, int64_t done, const float* scale_dev, float* mean, float* spread,
+                  float* member_pred, double* scores) {
+  const Dims& d = c->d;
+  const int M = B * d.N, E = a.members;
+  const bool shared = a.p_gcn == 0.f;
+  const int G = ens_group_size(d, M, E, !shared, c->ens_group);
+  const int64_t fslab = (int64_t)d.T * M * d.Hc;  // floats of one member's own features
+  FeatPlan f;
+  if (shared) f = feat_plan(c, B, consec);
+  else f.frows = f.grows = (int64_t)d.T * M;
+  const int64_t ring = infer_ring_floats(d, G, M);
+  if (c->ens_ring.grow(2 * ring * 4) != hipSuccess ||
+      c->fc_F.grow((shared ? f.frows * d.Hc : G * fslab) * 4) != hipSuccess ||
+      grow_all<HipAlloc>({{&c->fc_gcnA, f.grows * d.Hc * 4}, {&c->fc_gcnB, f.grows * d.Hc * 4}}) != hipSuccess ||
+      c->ens_pred.grow((int64_t)E * M * d.HfC * 4) != hipSuccess ||
+      (scores && c->fc_part.grow((int64_t)skill_blocks(d, B) * d.HfC * 4 * 4) != hipSuccess))
+    return fail(SMAML_ENOMEM, "hipMalloc of the ensemble buffers failed (batch " + std::to_string(B) + ", " +
+                                  std::to_string(G) + " members at a time)");
+  forecast_work(c, B);
+  if (shared) TRY(shared_features(c, s, theta, xt, consec, f));
+  else TRY(prep_gate_images(c, s, theta, 0));
+  EnsDrop ed = ens_drop(d, a, done);
+  // (a one-layer LSTM has no layer above to read a shared layer 0: its layer 0 is the top layer, whose h_T
+  // every member masks and hands to the head itself)
+  ed.share0 = shared && c->ens_share && d.L > 1 ? 1 : 0;
+  float* ringH = c->ens_ring.as<float>();
+  float* P = c->ens_pred.as<float>();
+  for (int e0 = 0; e0 < E; e0 += G) {
+    const int g = std::min(G, E - e0);
+    if (!shared)  // member e0 + z's masks are those of step e0 + z
+      for (int z = 0; z < g; ++z)
+        member_gcn_masked(c, s, xt, a, e0 + z, (uint64_t)done * d.T * d.N * d.Hc, c->w.F + (int64_t)z * fslab);
+    ed.e0 = e0;
+    // (the rings are laid out for g members, the cell states behind a full group's)
+    infer_waves_drop(c, s, theta, ringH, ringH + ring, g, shared ? 0 : fslab, ed, P + (int64_t)e0 * M * d.HfC);
+  }
+  TRY(raise_stats_lds(&c->ens_lds_set, E, ens_stats_prepare, "smaml_forecast_ensemble", "k_ens_stats"));
+  TIMED(c, s, C_MISC, 0,
+        launch_ens_stats(s, d, B, E, P, xt, scale_dev, mean, spread, member_pred, (int64_t)a.n * d.N * d.HfC,
+                         c->fc_part.as<float>(), scores, done == 0, scores ? score_weights(c) : nullptr));
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+// One pass of B origins (first of them `done` in the call's list) through the R cycles in lockstep: per cycle
+// the features and projections the window owes, the wavefront and head, and the forecast appended to every
+// origin's sequence.
+int rollout_pass(smaml_ctx* c, hipStream_t s, const ForecastCall& a, const RollPlan& p, int64_t done, int B,
+                 const float* scale_dev, float* traj, double* skill) {
+  const Dims& d = c->d;
+  const float* theta = a.theta;
+  const int M = B * d.N, sl = d.Hf + 1, S = p.S, R = a.cycles;
+  const int64_t ring = infer_ring_floats(d, 1, M), blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H;
+  const float* const* src = nullptr;
+  TRY(xtab_at(c, p.tab_src + done, &src));
+  RollSetup rs;
+  TRY(roll_setup(c, s, theta, B, R, c->ro_seq.as<float>(), src, p.fused, &rs));
+  Work& cw = c->w;
+  TIMED(c, s, C_MISC, 0, launch_rollout_init(s, rs.ra));
+  float* xg = c->ro_xg.as<float>();
+  float* xg0 = xg + (int64_t)S * slot;
+  float* F0 = c->ro_F0.as<float>();
+  float* ringH = c->fc_ring.as<float>();
+  float* pred = c->fc_pred.as<float>();
+  for (int j = 0; j < R; ++j) {
+    const float* const* wtab = nullptr;
+    const float* const* rtab = nullptr;
+    TRY(roll_tabs(c, p, j, B, &wtab, &rtab));
+    // the rows t >= 1 this cycle owes: the four position-independent convs, then layer 0's projection into
+    // their slots
+    const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
+    if (nrun > 0) {
+      gcn_rows(c, s, rs, p.fused, rtab, B, nrun, 0, cw.F);
+      xg_run_slots(c, s, theta, rs, cw.F, r0, nrun, S, M, xg, nullptr);
+      c->ro_stats[1] += (int64_t)B * nrun;
+      c->ro_stats[3] += (int64_t)B * nrun;
+    }
+    // the t = 0 rows aggregate over the graph (F3): per-layer chain over N-row blocks, as run_gcn's
+    gcn_chain(c, s, wtab, B, d.N, d.N, d.T * d.N, F0);
+    xg_rows(c, s, theta, rs, F0, M, xg0, nullptr);
+    c->ro_stats[2] += B;
+    c->ro_stats[3] += B;
+    XgDedup xd{};
+    xd.xg = xg;
+    xd.xg0 = xg0;
+    xd.src = theta;
+    xd.N = d.N;
+    xd.ring_S = S;
+    xd.ring_r0 = (j * sl) % S;
+    cw.xgd = xd;
+    infer_waves(c, s, theta, ringH, ringH + ring, pred);
+    float* out = traj ? traj + ((int64_t)done * R + j) * blkf : c->ro_blk.as<float>();
+    const int64_t ostride = traj ? (int64_t)R * blkf : blkf;
+    TIMED(c, s, C_MISC, 0, launch_rollout_append(s, rs.ra, j, a.gap, j + 1 < R, pred, out, ostride));
+    c->ro_stats[4] += 1;
+    if (skill)
+      TIMED(c, s, C_MISC, 0,
+            launch_rollout_skill(s, rs.ra, j, R, out, ostride, scale_dev, c->fc_part.as<float>(), skill, done == 0,
+                                 score_weights(c)));
+    c->ro_stats[0] += 1;
+  }
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+// floats of one member of a pass of M rows: rings, slot table with its t = 0 block, sequences, features
+int64_t rens_member_bytes(const Dims& d, int B, int R, bool per_member_F) {
+  const int64_t M = (int64_t)B * d.N, sl = d.Hf + 1;
+  const int64_t f = 2 * infer_ring_floats(d, 1, (int)M) + (d.T + 1) * M * 4 * d.H +
+                    (int64_t)B * (d.T + (int64_t)(R - 1) * sl) * d.N * d.Cin0 +
+                    (per_member_F ? (int64_t)d.T : std::max(d.T - 1, 1)) * M * d.Hc + M * d.Hc;
+  return f * 4;
+}
+
+// One pass of B origins (first of them `done`): the members G at a time over grid z, every (member, origin)
+// pair of a group in lockstep through the R cycles; then the pass's statistics from all E trajectories.
+// p_gcn == 0: rollout_pass's stages over g B samples, less what every member reads unchanged (with reuse: the
+// observed rows and cycle 0's t = 0 block, once for the pass). p_gcn > 0: ensemble_pass's masked GCN per
+// member and cycle.
+int rens_pass(smaml_ctx* c, hipStream_t s, const ForecastCall& a, const RollPlan& p, int64_t done, int B,
+              const float* scale_dev, float* member_traj, float* mean, float* spread, double* scores) {
+  const Dims& d = c->d;
+  const float* theta = a.theta;
+  const int M = B * d.N, sl = d.Hf + 1, S = p.S, E = a.members, R = a.cycles, TN = d.T * d.N;
+  const bool shared = a.p_gcn == 0.f, obs = shared && p.reuse;
+  const int64_t blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H, fslab = (int64_t)d.T * M * d.Hc;
+  const float* const* src = nullptr;
+  const float* const* otab = nullptr;
+  TRY(xtab_at(c, p.tab_src + done, &src));
+  TRY(xtab_at(c, p.tab_obs + done, &otab));
+  RollSetup rs;
+  TRY(roll_setup(c, s, theta, B, R, c->re_seq.as<float>(), src, shared && p.fused, &rs));
+  Work& cw = c->w;
+  float* Frun = cw.F;
+  float* xobs = c->re_obs.as<float>();
+  float* xobs0 = xobs + (int64_t)d.T * slot;
+  float* F0 = c->re_F0.as<float>();
+  int64_t* xg_blocks = &c->re_stats[4];
+  if (obs) {
+    // what every member reads unchanged: the observed rows 1 .. T - 1 (position-independent GCN, projection)
+    // and cycle 0's t = 0 block, once for the pass
+    const int nobs = d.T - 1;
+    if (nobs > 0) {
+      gcn_rows(c, s, rs, p.fused, otab, B, nobs, TN, Frun);
+      xg_rows(c, s, theta, rs, Frun, (int64_t)nobs * M, xobs + slot, xg_blocks);
+      c->re_stats[2] += (int64_t)B * nobs;
+    }
+    gcn_chain(c, s, src, B, d.N, d.N, TN, F0);
+    xg_rows(c, s, theta, rs, F0, M, xobs0, xg_blocks);
+    c->re_stats[3] += B;
+  }
+  float* traj = member_traj ? member_traj + done * R * blkf : c->re_traj.as<float>();
+  const int64_t tstride = (member_traj ? (int64_t)a.n : (int64_t)B) * R * blkf;  // floats between two members
+  EnsDrop ed = ens_drop(d, a, done);
+  float* P = c->ens_pred.as<float>();
+  for (int e0 = 0; e0 < E; e0 += p.G) {
+    const int g = std::min(p.G, E - e0);
+    float* ringH = c->ens_ring.as<float>();
+    float* ringC = ringH + infer_ring_floats(d, g, M);
+    float* xg = c->re_xg.as<float>();           // [S][g][M][4H]
+    float* xg0 = xg + (int64_t)S * g * slot;    // [g][M][4H]
+    TIMED(c, s, C_MISC, 0, launch_rollout_init(s, rs.ra, g));
+    c->re_stats[6] += 1;
+    for (int j = 0; j < R; ++j) {
+      const float* const* wtab = nullptr;
+      const float* const* rtab = nullptr;
+      TRY(roll_tabs(c, p, j, B, &wtab, &rtab));
+      const bool first_shared = obs && j == 0;  // every block of cycle 0 is in the shared table
+      if (!shared) {
+        // each member's GCN under its own kind-1 masks of step 64 j + e: all T rows of its window, every cycle
+        for (int z = 0; z < g; ++z)
+          member_gcn_masked(c, s, wtab + (int64_t)z * B, a, 64 * j + e0 + z, (uint64_t)done * TN * d.Hc,
+                            Frun + (int64_t)z * fslab);
+        c->re_stats[1] += (int64_t)g * B * (d.T - 1);
+        c->re_stats[3] += (int64_t)g * B;
+        cw.xgd = XgDedup{};
+      } else {
+        if (!first_shared) {
+          // the rows t >= 1 the members owe (with reuse: those they appended in the previous cycle), g B samples
+          // in one launch, time-major over the group, then into their slots; then their t = 0 blocks
+          const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
+          if (nrun > 0) {
+            gcn_rows(c, s, rs, p.fused, rtab, g * B, nrun, TN, Frun);
+            xg_run_slots(c, s, theta, rs, Frun, r0, nrun, S, (int64_t)g * M, xg, xg_blocks);
+            c->re_stats[1] += (int64_t)g * B * nrun;
+          }
+          gcn_chain(c, s, wtab, g * B, d.N, d.N, TN, F0);
+          xg_rows(c, s, theta, rs, F0, (int64_t)g * M, xg0, xg_blocks);
+          c->re_stats[3] += (int64_t)g * B;
+        }
+        XgDedup xd{};
+        xd.xg = xg;
+        xd.xg0 = first_shared ? xobs0 : xg0;
+        xd.src = theta;
+        xd.N = d.N;
+        xd.ring_S = S;
+        cw.xgd = xd;
+        ed.xg0_z = first_shared ? 0 : slot;
+        ed.xg_obs = obs ? xobs : nullptr;
+        ed.obs_rows = obs ? d.T : 0;
+        ed.ring_row = j * sl;
+      }
+      ed.e0 = 64 * j + e0;
+      // cycle 0's windows are the same in every member: with nothing masked below layer 0's output, layer 0 once
+      ed.share0 = shared && j == 0 && c->ens_share && d.L > 1 ? 1 : 0;
+      infer_waves_drop(c, s, theta, ringH, ringC, g, shared ? 0 : fslab, ed, P);
+      TIMED(c, s, C_MISC, 0,
+            launch_rollout_append(s, rs.ra, j, a.gap, j + 1 < R, P, traj + e0 * tstride + (int64_t)j * blkf,
+                                  (int64_t)R * blkf, g, tstride));
+      c->re_stats[5] += 1;
+      c->re_stats[0] += 1;
+    }
+  }
+  if (mean || spread || scores) {
+    TRY(raise_stats_lds(&c->rens_lds_set, E, rens_stats_prepare, "smaml_forecast_rollout_ensemble", "k_rens_stats"));
+    const int64_t off = done * R * blkf;
+    TIMED(c, s, C_MISC, 0,
+          launch_rens_stats(s, d, B, E, R * sl, traj, tstride, src, scale_dev, mean ? mean + off : nullptr,
+                            spread ? spread + off : nullptr, c->fc_part.as<float>(), scores, done == 0,
+                            scores ? score_weights(c) : nullptr));
+  }
+  HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
 
@@ -2261,62 +2743,26 @@ int smaml_set_tasks(smaml_ctx* c, int32_t ntasks, const float* const* features_h
 
 int smaml_forecast(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
                    int32_t nwin, int32_t batch, const float* scale_host, float* pred, double* skill) {
-  // (the checks that need no context first: they run without a device too)
-  if (!pred && !skill)
-    return fail(SMAML_EINVAL, "smaml_forecast: pred and skill are both NULL (nothing to compute)");
-  if (nwin <= 0 || batch <= 0 || !windows_host)
-    return fail(SMAML_EINVAL, "smaml_forecast: nwin and batch must be positive");
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_forecast"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  if (!theta || !aligned16(theta))
-    return fail(SMAML_EINVAL, "smaml_forecast: theta must be a 16-byte aligned device pointer");
-  if (task < 0 || task >= (int)c->feats.size()) return fail(SMAML_EINVAL, "smaml_forecast: task out of range");
-  const Dims& d = c->d;
-  const int B0 = std::min(batch, nwin);
-  if ((int64_t)d.T * B0 * d.N * 4 * d.H >= (1ll << 31))
-    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^31");
-  // a window needs its T input rows; scoring also the targets stream[w+T+1 .. w+T+Hf]
-  const int tt = c->t_total[task];
-  std::vector<const float*> ptrs(nwin);
-  for (int i = 0; i < nwin; ++i) {
-    const int wv = windows_host[i];
-    if (wv < 0 || wv + d.T > tt || (skill && wv + d.T + d.Hf >= tt))
-      return fail(SMAML_EINVAL, "smaml_forecast: window " + std::to_string(i) + " (start " + std::to_string(wv) +
-                                    (skill && wv >= 0 && wv + d.T <= tt ? ") has no targets in" : ") does not fit") +
-                                    " the stream of " + std::to_string(tt) + " steps");
-    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
-  }
-  TRY(ensure_device(c));
-  TRY(check_device_error(c));
+  ForecastCall a;
+  a.name = "smaml_forecast";
+  a.no_output = "pred and skill are both NULL (nothing to compute)";
+  a.any_output = pred || skill;
+  a.theta = theta;
+  a.list = windows_host;
+  a.n = nwin;
+  a.batch = batch;
+  a.task = task;
+  a.score = skill != nullptr;
+  a.scale_host = scale_host;
+  TRY(forecast_check(c, a));
   hipStream_t s = (hipStream_t)stream;
-  // The training state stays as it is: the forecast never touches the arena, and the workspace view
-  // (with the activations a pending smaml_backward / smaml_lstm_backward will consume) is put back.
-  const Work saved = c->w;
-  const int act = c->act_B;
-  auto run = [&]() -> int {
-    const float* scale_dev = nullptr;
-    if (skill && scale_host) {
-      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
-      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
-      scale_dev = c->fc_scale.as<float>();
-    }
-    TRY(upload_xtab(c, s, ptrs.data(), nwin));
-    for (int64_t done = 0; done < nwin; done += batch) {
-      const int B = (int)std::min<int64_t>(batch, nwin - done);
-      bool consec = B > 1;
-      for (int b = 1; b < B && consec; ++b) consec = windows_host[done + b] == windows_host[done] + b;
-      const float* const* xt = nullptr;
-      TRY(xtab_at(c, done, &xt));
-      TRY(forecast_pass(c, s, theta, xt, B, consec, pred ? pred + done * d.N * d.HfC : nullptr, scale_dev, skill,
-                        done == 0));
-    }
-    return SMAML_OK;
-  };
-  const int rc = run();
-  c->w = saved;
-  c->act_B = act;
-  return rc;
+  const int64_t per = (int64_t)c->d.N * c->d.HfC;  // floats of one window's prediction
+  return forecast_run(c, s, a, window_ptrs(c, a), [&](int64_t done, int B, const float* scale_dev) -> int {
+    const float* const* xt = nullptr;
+    TRY(xtab_at(c, done, &xt));
+    return forecast_pass(c, s, theta, xt, B, windows_consec(windows_host + done, B), pred ? pred + done * per : nullptr,
+                         scale_dev, skill, done == 0);
+  });
 }
 
 int64_t smaml_forecast_bytes(const smaml_ctx* c) {
@@ -2326,196 +2772,31 @@ int64_t smaml_forecast_bytes(const smaml_ctx* c) {
          c->ro_F0.cap + c->ro_blk.cap + c->re_seq.cap + c->re_xg.cap + c->re_obs.cap + c->re_F0.cap + c->re_traj.cap;
 }
 
-// ---- smaml_forecast_rollout: the forecast fed back in, cycle by cycle ------------------------------------
-namespace {
-// First private row whose features cycle j computes: with reuse only the rows the previous cycle appended
-// that the window's steps t >= 1 read (all of them when T > s; when T <= s the window holds fewer rows than a
-// cycle appends), else every row t >= 1 of the window. The run ends at row j s + T - 1.
-int roll_run_first(int j, int T, int sl, bool reuse) {
-  if (j == 0 || !reuse) return j * sl + 1;
-  return std::max(j * sl + 1, (j - 1) * sl + T);
-}
-
-struct RollPlan {
-  int R = 0, gap = 0, Bmax = 0, S = 0;
-  bool reuse = true, fused = false;
-  int64_t tab_src = 0, tab_cyc = 0;  // entries of the uploaded table: src[norig]; per cycle win[Bmax], run[Bmax]
-};
-
-// One pass of B origins (first of them `done` in the call's list) through the R cycles in lockstep.
-int rollout_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RollPlan& p, int64_t done, int B,
-                 const float* scale_dev, float* traj, double* skill) {
-  const Dims& d = c->d;
-  const int M = B * d.N, sl = d.Hf + 1, S = p.S;
-  const int64_t ring = infer_ring_floats(d, 1, M), blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H;
-  Work w{};
-  w.Z = 1;
-  w.B = B;
-  w.M = M;
-  w.F = c->fc_F.as<float>();
-  w.gcnA = c->fc_gcnA.as<float>();
-  w.gcnB = c->fc_gcnB.as<float>();
-  w.vcount = c->vcount;
-  w.kn = c->kn;
-  c->w = w;
-  TRY(prep_gate_images(c, s, theta, 0));
-  Work& cw = c->w;
-  const bool img = cw.gimg.th && cw.gimg_src == theta;
-  const char* gimg = img ? cw.gimg.th : nullptr;
-  const int64_t gimg_off = cw.gimg.off[0][0];
-  const GraphView gv = graph_view(c);
-  const int cin0 = c->po.lay[0].cin;
-  GcnWOff wo;
-  for (int k = 0; k < 4; ++k) {
-    wo.w[k] = c->go.w[k];
-    wo.b[k] = c->go.b[k];
-  }
-  if (p.fused) TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, c->gcn_wimg.as<char>()));
-  const float* const* src = nullptr;
-  TRY(xtab_at(c, p.tab_src + done, &src));
-  RollArgs ra{};
-  ra.seq = c->ro_seq.as<float>();
-  ra.seq_rows = d.T + (p.R - 1) * sl;
-  ra.seq_stride = (int64_t)ra.seq_rows * d.N * d.Cin0;
-  ra.src = src;
-  ra.B = B;
-  ra.N = d.N;
-  ra.Cin = d.Cin0;
-  ra.C = d.C;
-  ra.Hf = d.Hf;
-  ra.T = d.T;
-  TIMED(c, s, C_MISC, 0, launch_rollout_init(s, ra));
-  float* xg = c->ro_xg.as<float>();
-  float* xg0 = xg + (int64_t)S * slot;
-  float* F0 = c->ro_F0.as<float>();
-  float* Frun = c->fc_F.as<float>();
-  float* ringH = c->fc_ring.as<float>();
-  float* ringC = ringH + ring;
-  float* pred = c->fc_pred.as<float>();
-  float* bufs[2] = {cw.gcnA, cw.gcnB};
-  for (int j = 0; j < p.R; ++j) {
-    const float* const* wtab = nullptr;
-    const float* const* rtab = nullptr;
-    TRY(xtab_at(c, p.tab_cyc + (int64_t)j * 2 * p.Bmax, &wtab));
-    TRY(xtab_at(c, p.tab_cyc + ((int64_t)j * 2 + 1) * p.Bmax, &rtab));
-    // the rows t >= 1 this cycle owes: the four position-independent convs, then layer 0's projection into
-    // their slots (a run that wraps the table takes two launches)
-    const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
-    if (nrun > 0) {
-      if (p.fused) {
-        TIMED(c, s, C_GCN, 2.0 * B * nrun * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
-              launch_gcn_mlp_run(s, d, B, nrun, rtab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
-      } else {
-        const float* from = nullptr;
-        for (int k = 0; k < 4; ++k) {
-          const bool last = k == 3;
-          float* dst = last ? Frun : bufs[k & 1];
-          TIMED(c, s, C_GCN, 2.0 * B * nrun * d.N * c->go.cin[k] * d.Hc,
-                launch_gcn_layer(s, d, k, B, B, k == 0 ? rtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
-                                 c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, nrun * d.N, 0, nullptr));
-          from = dst;
-        }
-      }
-      for (int tau = 0; tau < nrun;) {
-        const int sl0 = (r0 + tau) % S, len = std::min(nrun - tau, S - sl0);
-        TIMED(c, s, C_XG, 2.0 * len * slot * cin0,
-              launch_xg_rows(s, d, cw, Frun + (int64_t)tau * M * d.Hc, (int64_t)len * M, theta, c->po, gimg, gimg_off,
-                             xg + (int64_t)sl0 * slot));
-        tau += len;
-      }
-      c->ro_stats[1] += (int64_t)B * nrun;
-      c->ro_stats[3] += (int64_t)B * nrun;
-    }
-    // the t = 0 rows aggregate over the graph (F3): per-layer chain over N-row blocks, as run_gcn's
-    const float* from = nullptr;
-    for (int k = 0; k < 4; ++k) {
-      const bool last = k == 3;
-      float* dst = last ? F0 : bufs[k & 1];
-      TIMED(c, s, C_GCN, 2.0 * M * c->go.cin[k] * d.Hc,
-            launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab : nullptr, from, dst, last, true, c->gcn + c->go.w[k],
-                             c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, d.N, d.N, nullptr, d.T * d.N));
-      from = dst;
-    }
-    TIMED(c, s, C_XG, 2.0 * slot * cin0, launch_xg_rows(s, d, cw, F0, M, theta, c->po, gimg, gimg_off, xg0));
-    c->ro_stats[2] += B;
-    c->ro_stats[3] += B;
-    XgDedup xd{};
-    xd.xg = xg;
-    xd.xg0 = xg0;
-    xd.src = theta;
-    xd.N = d.N;
-    xd.ring_S = S;
-    xd.ring_r0 = (j * sl) % S;
-    cw.xgd = xd;
-    for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
-      FwdWave wv{};
-      double fl = fwd_wave(d, cw, c->po, diag, 0, false, wv);
-      for (int q = 0; q < wv.n; ++q)  // (the projection's flops are counted in C_XG)
-        if (wv.l[q] == 0) fl -= 2.0 * M * 4 * d.H * wv.lo[q].cin;
-      TIMED(c, s, C_FWD, fl, launch_lstm_fwd_infer(s, d, cw, diag, theta, 0, c->po, ringH, ringC));
-    }
-    TIMED(c, s, C_HEAD, 2.0 * M * d.HfC * d.H,
-          launch_head_pred(s, d, cw, infer_ring_hT(d, ringH, 1, M), (int64_t)M * d.H, theta, 0, c->po, pred));
-    float* out = traj ? traj + ((int64_t)done * p.R + j) * blkf : c->ro_blk.as<float>();
-    const int64_t ostride = traj ? (int64_t)p.R * blkf : blkf;
-    TIMED(c, s, C_MISC, 0, launch_rollout_append(s, ra, j, p.gap, j + 1 < p.R, pred, out, ostride));
-    c->ro_stats[4] += 1;
-    if (skill)
-      TIMED(c, s, C_MISC, 0,
-            launch_rollout_skill(s, ra, j, p.R, out, ostride, scale_dev, c->fc_part.as<float>(), skill, done == 0,
-                                 score_weights(c)));
-    c->ro_stats[0] += 1;
-  }
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
-}
-}  // namespace
-
 int smaml_forecast_rollout(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* origins_host,
                            int32_t norig, int32_t batch, int32_t cycles, int32_t gap, const float* scale_host,
                            float* traj, double* skill) {
-  // (the checks that need no context first: they run without a device too)
-  if (!traj && !skill)
-    return fail(SMAML_EINVAL, "smaml_forecast_rollout: traj and skill are both NULL (nothing to compute)");
-  if (norig <= 0 || batch <= 0 || !origins_host)
-    return fail(SMAML_EINVAL, "smaml_forecast_rollout: norig and batch must be positive");
-  if (cycles <= 0) return fail(SMAML_EINVAL, "smaml_forecast_rollout: cycles must be positive");
-  if (gap != 0 && gap != 1)
-    return fail(SMAML_EINVAL, "smaml_forecast_rollout: gap must be 0 (persistence) or 1 (midpoint), got " +
-                                  std::to_string(gap));
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_forecast_rollout"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  if (!theta || !aligned16(theta))
-    return fail(SMAML_EINVAL, "smaml_forecast_rollout: theta must be a 16-byte aligned device pointer");
-  if (task < 0 || task >= (int)c->feats.size())
-    return fail(SMAML_EINVAL, "smaml_forecast_rollout: task out of range");
-  const Dims& d = c->d;
-  const int sl = d.Hf + 1, R = cycles, Bmax = std::min(batch, norig);
-  if ((int64_t)d.T * Bmax * d.N * 4 * d.H >= (1ll << 30))
-    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^30");
-  // an origin needs every exogenous row its fed-back windows read; scoring also the last cycle's targets
-  const int64_t tt = c->t_total[task];
-  const int64_t need_in = d.T + (int64_t)(R - 1) * sl, need_sc = d.T + (int64_t)R * sl;
-  for (int i = 0; i < norig; ++i) {
-    const int64_t o = origins_host[i];
-    if (o < 0 || o + need_in > tt || (skill && o + need_sc > tt))
-      return fail(SMAML_EINVAL, "smaml_forecast_rollout: origin " + std::to_string(i) + " (start " + std::to_string(o) +
-                                    (skill && o >= 0 && o + need_in <= tt ? ") has no targets for " : ") does not fit ") +
-                                    std::to_string(R) + " cycles in the stream of " + std::to_string(tt) + " steps");
-  }
-  TRY(ensure_device(c));
-  TRY(check_device_error(c));
+  ForecastCall a;
+  a.name = "smaml_forecast_rollout";
+  a.no_output = "traj and skill are both NULL (nothing to compute)";
+  a.any_output = traj || skill;
+  a.theta = theta;
+  a.list = origins_host;
+  a.n = norig;
+  a.batch = batch;
+  a.task = task;
+  a.score = skill != nullptr;
+  a.scale_host = scale_host;
+  a.rollout = true;
+  a.cycles = cycles;
+  a.gap = gap;
+  TRY(forecast_check(c, a));
   hipStream_t s = (hipStream_t)stream;
-  RollPlan p{};
-  p.R = R;
-  p.gap = gap;
-  p.Bmax = Bmax;
-  p.S = d.T;
-  p.reuse = c->roll_reuse != 0;
-  p.fused = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  const Dims& d = c->d;
+  const int sl = d.Hf + 1, R = cycles;
+  RollPlan p = roll_plan(c, a);
+  const int Bmax = p.Bmax;
   // every buffer at the largest pass's size before the first launch, so no table entry can dangle
-  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = need_in, nrun_max = std::max(d.T - 1, 1);
+  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = roll_seq_rows(d, R), nrun_max = std::max(d.T - 1, 1);
   const int64_t grows = p.fused ? Mx : nrun_max * Mx;
   if (c->ro_seq.grow(Bmax * seq_rows * d.N * d.Cin0 * 4) != hipSuccess ||
       c->ro_xg.grow((int64_t)(p.S + 1) * Mx * 4 * d.H * 4) != hipSuccess ||
@@ -2528,37 +2809,11 @@ int smaml_forecast_rollout(smaml_ctx* c, void* stream, const float* theta, int32
       (p.fused && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess))
     return fail(SMAML_ENOMEM, "hipMalloc of the rollout buffers failed (batch " + std::to_string(Bmax) + ", " +
                                   std::to_string(R) + " cycles)");
-  const int64_t rowf = (int64_t)d.N * d.Cin0;
-  std::vector<const float*> ptrs((size_t)norig + (size_t)R * 2 * Bmax);
-  for (int i = 0; i < norig; ++i) ptrs[i] = c->feats[task] + (int64_t)origins_host[i] * rowf;
-  p.tab_src = 0;
-  p.tab_cyc = norig;
-  const float* seq = c->ro_seq.as<float>();
-  for (int j = 0; j < R; ++j)
-    for (int b = 0; b < Bmax; ++b) {
-      const float* sb = seq + (int64_t)b * seq_rows * rowf;
-      ptrs[(size_t)norig + ((size_t)j * 2) * Bmax + b] = sb + (int64_t)j * sl * rowf;
-      ptrs[(size_t)norig + ((size_t)j * 2 + 1) * Bmax + b] = sb + (int64_t)roll_run_first(j, d.T, sl, p.reuse) * rowf;
-    }
+  const std::vector<const float*> ptrs = roll_table(c, a, c->ro_seq.as<float>(), p);
   for (auto& x : c->ro_stats) x = 0;
-  const Work saved = c->w;
-  const int act = c->act_B;
-  auto run = [&]() -> int {
-    const float* scale_dev = nullptr;
-    if (skill && scale_host) {
-      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
-      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
-      scale_dev = c->fc_scale.as<float>();
-    }
-    TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
-    for (int64_t done = 0; done < norig; done += batch)
-      TRY(rollout_pass(c, s, theta, p, done, (int)std::min<int64_t>(batch, norig - done), scale_dev, traj, skill));
-    return SMAML_OK;
-  };
-  const int rc = run();
-  c->w = saved;
-  c->act_B = act;
-  return rc;
+  return forecast_run(c, s, a, ptrs, [&](int64_t done, int B, const float* scale_dev) -> int {
+    return rollout_pass(c, s, a, p, done, B, scale_dev, traj, skill);
+  });
 }
 
 int smaml_rollout_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
@@ -2568,315 +2823,37 @@ int smaml_rollout_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_
   return SMAML_OK;
 }
 
-// ---- smaml_forecast_rollout_ensemble: MC-dropout members through the fed-back forecast -------------------
-namespace {
-constexpr int RENS_MAX_CYCLES = 1024;  // drop_site gives `step` 16 bits (step << 8 below kind << 24): 64 j + e < 2^16
-
-struct RensPlan {
-  int R = 0, gap = 0, E = 0, G = 0, Bmax = 0, Btail = 0, S = 0;
-  float p_gcn = 0.f, p_lstm = 0.f;
-  uint32_t seed = 0;
-  int64_t norig = 0;
-  bool reuse = true, fused = false;
-  // the uploaded table: src[norig] (origin rows), obs[norig] (the same one step on), then for the pass size
-  // Bmax and, behind it, for the last pass's Btail: per cycle win[G * B], run[G * B], entry z * B + b
-  int64_t tab_src = 0, tab_obs = 0, tab_cyc[2] = {0, 0};
-};
-
-// floats of one member of a pass of M rows: rings, slot table with its t = 0 block, sequences, features
-int64_t rens_member_bytes(const Dims& d, int B, int R, bool per_member_F) {
-  const int64_t M = (int64_t)B * d.N, sl = d.Hf + 1;
-  const int64_t f = 2 * infer_ring_floats(d, 1, (int)M) + (d.T + 1) * M * 4 * d.H +
-                    (int64_t)B * (d.T + (int64_t)(R - 1) * sl) * d.N * d.Cin0 +
-                    (per_member_F ? (int64_t)d.T : std::max(d.T - 1, 1)) * M * d.Hc + M * d.Hc;
-  return f * 4;
-}
-
-// One pass of B origins (first of them `done`): the members G at a time over grid z, every (member, origin)
-// pair of a group in lockstep through the R cycles; then the pass's statistics from all E trajectories.
-int rens_pass(smaml_ctx* c, hipStream_t s, const float* theta, const RensPlan& p, int64_t done, int B,
-              const float* scale_dev, float* member_traj, float* mean, float* spread, double* scores) {
-  const Dims& d = c->d;
-  const int M = B * d.N, sl = d.Hf + 1, S = p.S, E = p.E;
-  const bool shared = p.p_gcn == 0.f, obs = shared && p.reuse;
-  const int64_t blkf = (int64_t)sl * d.N * d.C, slot = (int64_t)M * 4 * d.H, fslab = (int64_t)d.T * M * d.Hc;
-  Work w{};
-  w.Z = 1;
-  w.B = B;
-  w.M = M;
-  w.F = c->fc_F.as<float>();
-  w.gcnA = c->fc_gcnA.as<float>();
-  w.gcnB = c->fc_gcnB.as<float>();
-  w.vcount = c->vcount;
-  w.kn = c->kn;
-  c->w = w;
-  TRY(prep_gate_images(c, s, theta, 0));
-  Work& cw = c->w;
-  const bool img = cw.gimg.th && cw.gimg_src == theta;
-  const char* gimg = img ? cw.gimg.th : nullptr;
-  const int64_t gimg_off = cw.gimg.off[0][0];
-  const GraphView gv = graph_view(c);
-  const int cin0 = c->po.lay[0].cin;
-  GcnWOff wo;
-  for (int k = 0; k < 4; ++k) {
-    wo.w[k] = c->go.w[k];
-    wo.b[k] = c->go.b[k];
-  }
-  if (shared && p.fused) TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, c->gcn_wimg.as<char>()));
-  float* bufs[2] = {cw.gcnA, cw.gcnB};
-  float* Frun = c->fc_F.as<float>();
-  // the per-layer chain over `ns` samples of rps rows each (the first ell_rows of them aggregate over the
-  // graph), time-major into dst over all ns samples; in chunks of samples whose buffers stay below 2^30 bytes
-  // (the layer kernel's loaders index in 32 bits)
-  auto gcn_chain = [&](const float* const* tab, int ns, int rps, int ell_rows, float* dst) {
-    const int cs = (int)std::max<int64_t>(1, (1ll << 28) / ((int64_t)rps * d.Hc));
-    for (int s0 = 0; s0 < ns; s0 += cs) {
-      const int n = std::min(cs, ns - s0);
-      const float* from = nullptr;
-      for (int k = 0; k < 4; ++k) {
-        const bool last = k == 3;
-        float* to = last ? dst + (int64_t)s0 * d.N * d.Hc : bufs[k & 1];
-        TIMED(c, s, C_GCN, 2.0 * n * rps * c->go.cin[k] * d.Hc,
-              launch_gcn_layer(s, d, k, n, ns, k == 0 ? tab + s0 : nullptr, from, to, last, true, c->gcn + c->go.w[k],
-                               c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, ell_rows, nullptr,
-                               d.T * d.N));
-        from = to;
-      }
-    }
-  };
-  // layer 0's projection of plain rows, in launches whose output stays below 2^32 bytes (k_xg_dedup's stores
-  // index in 32 bits)
-  auto xg_rows = [&](const float* F, int64_t rows, float* out) {
-    const int64_t cr = ((1ll << 30) / (4 * d.H) - 1) / 256 * 256;
-    for (int64_t r = 0; r < rows; r += cr) {
-      const int64_t n = std::min(cr, rows - r);
-      TIMED(c, s, C_XG, 2.0 * n * 4 * d.H * cin0,
-            launch_xg_rows(s, d, cw, F + r * d.Hc, n, theta, c->po, gimg, gimg_off, out + r * 4 * d.H));
-    }
-    c->re_stats[4] += rows / d.N;
-  };
-  const float* const* src = nullptr;
-  const float* const* otab = nullptr;
-  TRY(xtab_at(c, p.tab_src + done, &src));
-  TRY(xtab_at(c, p.tab_obs + done, &otab));
-  float* xobs = c->re_obs.as<float>();
-  float* xobs0 = xobs + (int64_t)d.T * slot;
-  float* F0 = c->re_F0.as<float>();
-  if (obs) {
-    // what every member reads unchanged: the observed rows 1 .. T - 1 (position-independent GCN, projection)
-    // and cycle 0's t = 0 block, once for the pass
-    const int nobs = d.T - 1;
-    if (nobs > 0) {
-      if (p.fused)
-        TIMED(c, s, C_GCN, 2.0 * B * nobs * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
-              launch_gcn_mlp_run(s, d, B, nobs, otab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
-      else
-        gcn_chain(otab, B, nobs * d.N, 0, Frun);
-      xg_rows(Frun, (int64_t)nobs * M, xobs + slot);
-      c->re_stats[2] += (int64_t)B * nobs;
-    }
-    gcn_chain(src, B, d.N, d.N, F0);
-    xg_rows(F0, M, xobs0);
-    c->re_stats[3] += B;
-  }
-  RollArgs ra{};
-  ra.seq = c->re_seq.as<float>();
-  ra.seq_rows = d.T + (p.R - 1) * sl;
-  ra.seq_stride = (int64_t)ra.seq_rows * d.N * d.Cin0;
-  ra.src = src;
-  ra.B = B;
-  ra.N = d.N;
-  ra.Cin = d.Cin0;
-  ra.C = d.C;
-  ra.Hf = d.Hf;
-  ra.T = d.T;
-  const int which = B == p.Bmax ? 0 : 1;  // (the table set laid out for this pass size)
-  const int64_t tabGB = (int64_t)p.G * B;
-  float* traj = member_traj ? member_traj + done * p.R * blkf : c->re_traj.as<float>();
-  const int64_t tstride = (member_traj ? p.norig : (int64_t)B) * p.R * blkf;  // floats between two members
-  EnsDrop ed{};
-  ed.seed = p.seed;
-  ed.thr = (uint32_t)std::lround((double)p.p_lstm * 16777216.0);
-  ed.sc = 1.f / (1.f - p.p_lstm);
-  ed.row0 = done * d.N;
-  ed.Mtot = p.norig * d.N;
-  const uint32_t thr_gcn = (uint32_t)std::lround((double)p.p_gcn * 16777216.0);
-  float* P = c->ens_pred.as<float>();
-  for (int e0 = 0; e0 < E; e0 += p.G) {
-    const int g = std::min(p.G, E - e0);
-    const int64_t ring = infer_ring_floats(d, g, M);
-    float* ringH = c->ens_ring.as<float>();
-    float* ringC = ringH + ring;
-    float* xg = c->re_xg.as<float>();           // [S][g][M][4H]
-    float* xg0 = xg + (int64_t)S * g * slot;    // [g][M][4H]
-    TIMED(c, s, C_MISC, 0, launch_rollout_init(s, ra, g));
-    c->re_stats[6] += 1;
-    for (int j = 0; j < p.R; ++j) {
-      const float* const* wtab = nullptr;
-      const float* const* rtab = nullptr;
-      TRY(xtab_at(c, p.tab_cyc[which] + (int64_t)j * 2 * tabGB, &wtab));
-      TRY(xtab_at(c, p.tab_cyc[which] + ((int64_t)j * 2 + 1) * tabGB, &rtab));
-      const bool first_shared = obs && j == 0;  // every block of cycle 0 is in the shared table
-      if (!shared) {
-        // each member's GCN under its own kind-1 masks of step 64 j + e (smaml_forecast_ensemble's path): all T
-        // rows of its window, every cycle
-        const int rps = d.T * d.N;
-        for (int z = 0; z < g; ++z) {
-          const float* from = nullptr;
-          for (int k = 0; k < 4; ++k) {
-            const bool last = k == 3;
-            float* to = last ? Frun + (int64_t)z * fslab : bufs[k & 1];
-            TIMED(c, s, C_GCN, 2.0 * B * rps * c->go.cin[k] * d.Hc,
-                  launch_gcn_layer(s, d, k, B, B, k == 0 ? wtab + (int64_t)z * B : nullptr, from, to, last, true,
-                                   c->gcn + c->go.w[k], c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, rps, d.N,
-                                   nullptr));
-            if (!last)
-              TIMED(c, s, C_GCN, 0,
-                    launch_ens_dropout(s, to, (int64_t)B * rps * d.Hc, 1, p.seed, 1, 64 * j + e0 + z, k, thr_gcn,
-                                       1.f / (1.f - p.p_gcn), (uint64_t)done * rps * d.Hc));
-            from = to;
-          }
-        }
-        c->re_stats[1] += (int64_t)g * B * (d.T - 1);
-        c->re_stats[3] += (int64_t)g * B;
-        cw.xgd = XgDedup{};
-      } else {
-        if (!first_shared) {
-          // the rows t >= 1 the members owe (with reuse: those they appended in the previous cycle), g B samples
-          // in one launch, time-major over the group, then into their slots (a run that wraps takes two)
-          const int r0 = roll_run_first(j, d.T, sl, p.reuse), nrun = j * sl + d.T - r0;
-          if (nrun > 0) {
-            if (p.fused)
-              TIMED(c, s, C_GCN, 2.0 * g * B * nrun * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
-                    launch_gcn_mlp_run(s, d, g * B, nrun, rtab, c->gcn, wo, c->gcn_wimg.as<char>(), Frun));
-            else
-              gcn_chain(rtab, g * B, nrun * d.N, 0, Frun);
-            for (int tau = 0; tau < nrun;) {
-              const int sl0 = (r0 + tau) % S, len = std::min(nrun - tau, S - sl0);
-              xg_rows(Frun + (int64_t)tau * g * M * d.Hc, (int64_t)len * g * M, xg + (int64_t)sl0 * g * slot);
-              tau += len;
-            }
-            c->re_stats[1] += (int64_t)g * B * nrun;
-          }
-          gcn_chain(wtab, g * B, d.N, d.N, F0);
-          xg_rows(F0, (int64_t)g * M, xg0);
-          c->re_stats[3] += (int64_t)g * B;
-        }
-        XgDedup xd{};
-        xd.xg = xg;
-        xd.xg0 = first_shared ? xobs0 : xg0;
-        xd.src = theta;
-        xd.N = d.N;
-        xd.ring_S = S;
-        cw.xgd = xd;
-        ed.xg0_z = first_shared ? 0 : slot;
-        ed.xg_obs = obs ? xobs : nullptr;
-        ed.obs_rows = obs ? d.T : 0;
-        ed.ring_row = j * sl;
-      }
-      ed.e0 = 64 * j + e0;
-      // cycle 0's windows are the same in every member: with nothing masked below layer 0's output, layer 0 once
-      ed.share0 = shared && j == 0 && c->ens_share && d.L > 1 ? 1 : 0;
-      for (int diag = 0; diag < d.T + d.L - 1; ++diag) {
-        FwdWave wv{};
-        double fl = 0.0;
-        fwd_wave(d, cw, c->po, diag, 0, false, wv);
-        for (int q = 0; q < wv.n; ++q) {
-          const double k1 = (wv.l[q] == 0 && shared ? 0 : wv.lo[q].cin) + (wv.t[q] > 0 ? d.H : 0);
-          fl += 2.0 * (wv.l[q] == 0 && ed.share0 ? 1 : g) * M * 4 * d.H * k1;
-        }
-        TIMED(c, s, C_FWD, fl,
-              launch_lstm_fwd_infer_drop(s, d, cw, diag, theta, c->po, ringH, ringC, g, shared ? 0 : fslab, ed));
-      }
-      float* hT = ringH + (int64_t)(2 * (d.L - 1) + ((d.T - 1) & 1)) * g * M * d.H;
-      if (ed.thr)
-        TIMED(c, s, C_HEAD, 0,
-              launch_ens_dropout(s, hT, (int64_t)M * d.H, g, p.seed, 3, ed.e0, 0, ed.thr, ed.sc,
-                                 (uint64_t)ed.row0 * d.H));
-      Work hw = cw;
-      hw.Z = g;
-      TIMED(c, s, C_HEAD, 2.0 * g * M * d.HfC * d.H,
-            launch_head_pred(s, d, hw, hT, (int64_t)M * d.H, theta, 0, c->po, P));
-      TIMED(c, s, C_MISC, 0,
-            launch_rollout_append(s, ra, j, p.gap, j + 1 < p.R, P, traj + e0 * tstride + (int64_t)j * blkf,
-                                  (int64_t)p.R * blkf, g, tstride));
-      c->re_stats[5] += 1;
-      c->re_stats[0] += 1;
-    }
-  }
-  if (mean || spread || scores) {
-    if (E > 32 && !c->rens_lds_set) {
-      const hipError_t st = rens_stats_prepare();
-      if (st != hipSuccess)
-        return fail(SMAML_EHIP, std::string("smaml_forecast_rollout_ensemble: raising k_rens_stats's dynamic LDS limit "
-                                            "to 64 KB (more than 32 members) failed: ") + hipGetErrorString(st));
-      c->rens_lds_set = true;
-    }
-    const int64_t off = done * p.R * blkf;
-    TIMED(c, s, C_MISC, 0,
-          launch_rens_stats(s, d, B, E, p.R * sl, traj, tstride, src, scale_dev, mean ? mean + off : nullptr,
-                            spread ? spread + off : nullptr, c->fc_part.as<float>(), scores, done == 0,
-                            scores ? score_weights(c) : nullptr));
-  }
-  HIP_TRY(hipGetLastError());
-  return SMAML_OK;
-}
-}  // namespace
-
 int smaml_forecast_rollout_ensemble(smaml_ctx* c, void* stream, const float* theta, int32_t task,
                                     const int32_t* origins_host, int32_t norig, int32_t batch, int32_t cycles,
                                     int32_t gap, int32_t members, float p_gcn, float p_lstm, uint32_t seed,
                                     const float* scale_host, float* member_traj, float* mean, float* spread,
                                     double* scores) {
-  const std::string fn = "smaml_forecast_rollout_ensemble: ";
-  // (the checks that need no context first: they run without a device too)
-  if (!member_traj && !mean && !spread && !scores)
-    return fail(SMAML_EINVAL, fn + "member_traj, mean, spread and scores are all NULL (nothing to compute)");
-  if (norig <= 0 || batch <= 0 || !origins_host) return fail(SMAML_EINVAL, fn + "norig and batch must be positive");
-  if (members < 1 || members > 64)
-    return fail(SMAML_EINVAL, fn + "members must be in 1..64, got " + std::to_string(members));
-  if (cycles < 1 || cycles > RENS_MAX_CYCLES)
-    return fail(SMAML_EINVAL, fn + "cycles must be in 1.." + std::to_string(RENS_MAX_CYCLES) +
-                                  " (the mask site's step 64 j + e has 16 bits), got " + std::to_string(cycles));
-  if (!(p_gcn >= 0.f && p_gcn < 1.f) || !(p_lstm >= 0.f && p_lstm < 1.f))
-    return fail(SMAML_EINVAL, fn + "dropout probabilities must be in [0, 1)");
-  if (gap != 0 && gap != 1)
-    return fail(SMAML_EINVAL, fn + "gap must be 0 (persistence) or 1 (midpoint), got " + std::to_string(gap));
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_forecast_rollout_ensemble"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  if (!theta || !aligned16(theta)) return fail(SMAML_EINVAL, fn + "theta must be a 16-byte aligned device pointer");
-  if (task < 0 || task >= (int)c->feats.size()) return fail(SMAML_EINVAL, fn + "task out of range");
-  const Dims& d = c->d;
-  const int sl = d.Hf + 1, R = cycles, E = members, Bmax = std::min(batch, norig);
-  if ((int64_t)d.T * Bmax * d.N * 4 * d.H >= (1ll << 30))
-    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^30");
-  const int64_t tt = c->t_total[task];
-  const int64_t need_in = d.T + (int64_t)(R - 1) * sl, need_sc = d.T + (int64_t)R * sl;
-  for (int i = 0; i < norig; ++i) {
-    const int64_t o = origins_host[i];
-    if (o < 0 || o + need_in > tt || (scores && o + need_sc > tt))
-      return fail(SMAML_EINVAL, fn + "origin " + std::to_string(i) + " (start " + std::to_string(o) +
-                                    (scores && o >= 0 && o + need_in <= tt ? ") has no targets for " : ") does not fit ") +
-                                    std::to_string(R) + " cycles in the stream of " + std::to_string(tt) + " steps");
-  }
-  TRY(ensure_device(c));
-  TRY(check_device_error(c));
+  ForecastCall a;
+  a.name = "smaml_forecast_rollout_ensemble";
+  a.no_output = "member_traj, mean, spread and scores are all NULL (nothing to compute)";
+  a.any_output = member_traj || mean || spread || scores;
+  a.theta = theta;
+  a.list = origins_host;
+  a.n = norig;
+  a.batch = batch;
+  a.task = task;
+  a.score = scores != nullptr;
+  a.scale_host = scale_host;
+  a.rollout = true;
+  a.cycles = cycles;
+  a.gap = gap;
+  a.ens = true;
+  a.members = members;
+  a.p_gcn = p_gcn;
+  a.p_lstm = p_lstm;
+  a.seed = seed;
+  TRY(forecast_check(c, a));
   hipStream_t s = (hipStream_t)stream;
+  const Dims& d = c->d;
+  const int sl = d.Hf + 1, R = cycles, E = members;
   const bool shared = p_gcn == 0.f;
-  RensPlan p{};
-  p.R = R;
-  p.gap = gap;
-  p.E = E;
-  p.Bmax = Bmax;
-  p.Btail = norig % batch ? norig % batch : Bmax;
-  p.S = d.T;
-  p.p_gcn = p_gcn;
-  p.p_lstm = p_lstm;
-  p.seed = seed;
-  p.norig = norig;
-  p.reuse = c->roll_reuse != 0;
-  p.fused = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  RollPlan p = roll_plan(c, a);
+  const int Bmax = p.Bmax;
   // members per launch set: option ens_group, else as many as fit the budget (at least one)
   if (c->ens_group > 0) p.G = std::min(c->ens_group, E);
   else if (c->ens_group == 0) p.G = E;
@@ -2885,7 +2862,7 @@ int smaml_forecast_rollout_ensemble(smaml_ctx* c, void* stream, const float* the
         1, std::min<int64_t>(E, (c->roll_ens_budget_mb << 20) / rens_member_bytes(d, Bmax, R, !shared)));
   const int G = p.G;
   // every buffer at the largest pass's and group's size before the first launch, so no table entry can dangle
-  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = need_in, nrun_max = std::max(d.T - 1, 1);
+  const int64_t Mx = (int64_t)Bmax * d.N, seq_rows = roll_seq_rows(d, R), nrun_max = std::max(d.T - 1, 1);
   const int64_t blkf = (int64_t)sl * d.N * d.C;
   // (the per-layer chain's ping-pong buffers: a chunk of samples below 2^28 floats, or one member's T-row window)
   const int64_t crows = p.fused ? 1 : nrun_max;  // (the fused stack takes the runs: only the t = 0 rows chain)
@@ -2905,48 +2882,11 @@ int smaml_forecast_rollout_ensemble(smaml_ctx* c, void* stream, const float* the
       (shared && p.fused && c->gcn_wimg.grow(gcn_wimg_bytes(d)) != hipSuccess))
     return fail(SMAML_ENOMEM, "hipMalloc of the ensemble-rollout buffers failed (batch " + std::to_string(Bmax) + ", " +
                                   std::to_string(R) + " cycles, " + std::to_string(G) + " members at a time)");
-  const int64_t rowf = (int64_t)d.N * d.Cin0;
-  const int nset = p.Btail != Bmax ? 2 : 1;
-  std::vector<const float*> ptrs((size_t)2 * norig + (size_t)R * 2 * G * (Bmax + (nset == 2 ? p.Btail : 0)));
-  for (int i = 0; i < norig; ++i) {
-    ptrs[i] = c->feats[task] + (int64_t)origins_host[i] * rowf;
-    ptrs[(size_t)norig + i] = ptrs[i] + rowf;
-  }
-  p.tab_src = 0;
-  p.tab_obs = norig;
-  const float* seq = c->re_seq.as<float>();
-  int64_t at = 2 * (int64_t)norig;
-  for (int k = 0; k < nset; ++k) {
-    const int B = k == 0 ? Bmax : p.Btail;
-    p.tab_cyc[k] = at;
-    for (int j = 0; j < R; ++j)
-      for (int zb = 0; zb < G * B; ++zb) {
-        const float* sb = seq + (int64_t)zb * seq_rows * rowf;
-        ptrs[(size_t)(at + ((int64_t)j * 2) * G * B + zb)] = sb + (int64_t)j * sl * rowf;
-        ptrs[(size_t)(at + ((int64_t)j * 2 + 1) * G * B + zb)] = sb + (int64_t)roll_run_first(j, d.T, sl, p.reuse) * rowf;
-      }
-    at += (int64_t)R * 2 * G * B;
-  }
+  const std::vector<const float*> ptrs = roll_table(c, a, c->re_seq.as<float>(), p);
   for (auto& x : c->re_stats) x = 0;
-  const Work saved = c->w;
-  const int act = c->act_B;
-  auto run = [&]() -> int {
-    const float* scale_dev = nullptr;
-    if (scores && scale_host) {
-      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
-      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
-      scale_dev = c->fc_scale.as<float>();
-    }
-    TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
-    for (int64_t done = 0; done < norig; done += batch)
-      TRY(rens_pass(c, s, theta, p, done, (int)std::min<int64_t>(batch, norig - done), scale_dev, member_traj,
-                    mean, spread, scores));
-    return SMAML_OK;
-  };
-  const int rc = run();
-  c->w = saved;
-  c->act_B = act;
-  return rc;
+  return forecast_run(c, s, a, ptrs, [&](int64_t done, int B, const float* scale_dev) -> int {
+    return rens_pass(c, s, a, p, done, B, scale_dev, member_traj, mean, spread, scores);
+  });
 }
 
 int smaml_rollout_ensemble_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
@@ -2959,74 +2899,33 @@ int smaml_rollout_ensemble_stats(const smaml_ctx* c, int64_t* counts, int32_t ca
 int smaml_forecast_ensemble(smaml_ctx* c, void* stream, const float* theta, int32_t task, const int32_t* windows_host,
                             int32_t nwin, int32_t batch, int32_t members, float p_gcn, float p_lstm, uint32_t seed,
                             const float* scale_host, float* mean, float* spread, float* member_pred, double* scores) {
-  // (the checks that need no context first: they run without a device too)
-  if (!mean && !spread && !member_pred && !scores)
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: mean, spread, member_pred and scores are all NULL");
-  if (nwin <= 0 || batch <= 0 || !windows_host)
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: nwin and batch must be positive");
-  if (members < 1 || members > 64)
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: members must be in 1..64, got " + std::to_string(members));
-  if (!(p_gcn >= 0.f && p_gcn < 1.f) || !(p_lstm >= 0.f && p_lstm < 1.f))
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: dropout probabilities must be in [0, 1)");
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_forecast_ensemble"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  if (!theta || !aligned16(theta))
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: theta must be a 16-byte aligned device pointer");
-  if (task < 0 || task >= (int)c->feats.size())
-    return fail(SMAML_EINVAL, "smaml_forecast_ensemble: task out of range");
-  const Dims& d = c->d;
-  const int B0 = std::min(batch, nwin);
-  if ((int64_t)d.T * B0 * d.N * 4 * d.H >= (1ll << 31))
-    return fail(SMAML_EINVAL, "batch too large: T*B*N*4H must stay below 2^31");
-  const int tt = c->t_total[task];
-  std::vector<const float*> ptrs(nwin);
-  for (int i = 0; i < nwin; ++i) {
-    const int wv = windows_host[i];
-    if (wv < 0 || wv + d.T > tt || (scores && wv + d.T + d.Hf >= tt))
-      return fail(SMAML_EINVAL, "smaml_forecast_ensemble: window " + std::to_string(i) + " (start " +
-                                    std::to_string(wv) +
-                                    (scores && wv >= 0 && wv + d.T <= tt ? ") has no targets in" : ") does not fit") +
-                                    " the stream of " + std::to_string(tt) + " steps");
-    ptrs[i] = c->feats[task] + (int64_t)wv * d.N * d.Cin0;
-  }
-  TRY(ensure_device(c));
-  TRY(check_device_error(c));
+  ForecastCall a;
+  a.name = "smaml_forecast_ensemble";
+  a.no_output = "mean, spread, member_pred and scores are all NULL";
+  a.any_output = mean || spread || member_pred || scores;
+  a.theta = theta;
+  a.list = windows_host;
+  a.n = nwin;
+  a.batch = batch;
+  a.task = task;
+  a.score = scores != nullptr;
+  a.scale_host = scale_host;
+  a.ens = true;
+  a.members = members;
+  a.p_gcn = p_gcn;
+  a.p_lstm = p_lstm;
+  a.seed = seed;
+  TRY(forecast_check(c, a));
   hipStream_t s = (hipStream_t)stream;
-  // as smaml_forecast: the workspace view of the training state is put back
-  const Work saved = c->w;
-  const int act = c->act_B;
-  auto run = [&]() -> int {
-    const float* scale_dev = nullptr;
-    if (scores && scale_host) {
-      HIP_TRY(c->fc_scale.grow((int64_t)d.C * 4));
-      TRY(c->stage.upload(s, c->fc_scale.ptr, scale_host, (int64_t)d.C * 4));
-      scale_dev = c->fc_scale.as<float>();
-    }
-    TRY(upload_xtab(c, s, ptrs.data(), nwin));
-    EnsArgs a{};
-    a.E = members;
-    a.p_gcn = p_gcn;
-    a.p_lstm = p_lstm;
-    a.seed = seed;
-    a.nwin = nwin;
-    for (int64_t done = 0; done < nwin; done += batch) {
-      const int B = (int)std::min<int64_t>(batch, nwin - done);
-      bool consec = B > 1;
-      for (int b = 1; b < B && consec; ++b) consec = windows_host[done + b] == windows_host[done] + b;
-      const float* const* xt = nullptr;
-      TRY(xtab_at(c, done, &xt));
-      a.done = done;
-      const int64_t off = done * d.N * d.HfC;
-      TRY(ensemble_pass(c, s, theta, xt, B, consec, a, scale_dev, mean ? mean + off : nullptr,
-                        spread ? spread + off : nullptr, member_pred ? member_pred + off : nullptr, scores));
-    }
-    return SMAML_OK;
-  };
-  const int rc = run();
-  c->w = saved;
-  c->act_B = act;
-  return rc;
+  const int64_t per = (int64_t)c->d.N * c->d.HfC;
+  return forecast_run(c, s, a, window_ptrs(c, a), [&](int64_t done, int B, const float* scale_dev) -> int {
+    const float* const* xt = nullptr;
+    TRY(xtab_at(c, done, &xt));
+    const int64_t off = done * per;
+    return ensemble_pass(c, s, theta, xt, B, windows_consec(windows_host + done, B), a, done, scale_dev,
+                         mean ? mean + off : nullptr, spread ? spread + off : nullptr,
+                         member_pred ? member_pred + off : nullptr, scores);
+  });
 }
 
 int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,
@@ -3730,7 +3629,6 @@ int smaml_adamw_step(smaml_ctx* c, void* stream, float* theta, const float* grad
   HIP_TRY(hipGetLastError());
   return SMAML_OK;
 }
-
 
 // ---- finer-grained entry points --------------------------------------
 

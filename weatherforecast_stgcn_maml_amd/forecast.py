@@ -139,6 +139,54 @@ class _score_weights:
         return False
 
 
+def _setup(who, model, features, edge_index, edge_weight, stats, ctx, entries, default_entries, device_only=True,
+           prepare_empty=False):
+    """What the four forecast calls share before their library call: the device check, ``features`` as a float32
+    device tensor, the window starts or origins (``entries``, or ``default_entries(t_total, T, Hf)``) and -- unless
+    there are none: nothing is asked of a context then, but for its graph and parameters with ``prepare_empty``,
+    which ``forecast`` has always set -- the context (``ctx``, or the model's own) holding the
+    graph, the GCN parameters and the stream as task 0, ``theta``, and the ``stats`` as ``std`` (numpy) and the
+    device tensors ``units() = (scale_t, shift_t)`` that take normalised output to physical units."""
+    import torch
+    from types import SimpleNamespace
+
+    from . import _capi
+    from .model import _set_graph
+
+    dev = next(model.parameters()).device
+    if device_only and dev.type != "cuda":
+        raise _capi.SmamlError(-1, f"{who} runs on a HIP device only")
+    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
+    f = f.to(dev, torch.float32).contiguous()
+    T = model.base_stgcn.window_size
+    Hf, C = model.forecast_horizon, model.out_channels
+    t_total, N = int(f.shape[0]), int(f.shape[1])
+    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
+    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
+    if ew is not None and not torch.is_tensor(ew):
+        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
+    e = default_entries(t_total, T, Hf) if entries is None else np.asarray(entries, np.int32).reshape(-1)
+    c = SimpleNamespace(dev=dev, N=N, Hf=Hf, C=C, entries=e)
+    if e.size == 0 and not prepare_empty:
+        return c
+    if ctx is None:
+        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
+    else:
+        dims = model.dims(N)
+        _set_graph(ctx, ei, ew)
+        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
+        ctx.set_gcn_params(gflat)
+        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
+    if e.size == 0:
+        return c
+    ctx.set_tasks([f])
+    mean, c.std = _stats(stats, C)
+    c.ctx, c.theta = ctx, theta
+    c.units = lambda: (torch.from_numpy(c.std.astype(np.float32)).to(dev),
+                       torch.from_numpy(mean.astype(np.float32)).to(dev))
+    return c
+
+
 def forecast(model, features, edge_index, stats=None, windows=None, batch: int = 64, score: bool = True,
              return_pred: bool = True, ctx=None,
              edge_weight=None, node_weights=None) -> ForecastResult:
@@ -156,43 +204,22 @@ def forecast(model, features, edge_index, stats=None, windows=None, batch: int =
     import torch
 
     from . import _capi
-    from .model import _set_graph
 
     if not score and not return_pred:
         raise ValueError("forecast(score=False, return_pred=False) has nothing to return")
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise _capi.SmamlError(-1, "forecast runs on a HIP device only")
-    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
-    f = f.to(dev, torch.float32).contiguous()
-    T = model.base_stgcn.window_size
-    Hf, C = model.forecast_horizon, model.out_channels
-    t_total, N = int(f.shape[0]), int(f.shape[1])
-    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
-    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
-    if ew is not None and not torch.is_tensor(ew):
-        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
-    if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
-    else:
-        dims = model.dims(N)
-        _set_graph(ctx, ei, ew)
-        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
-        ctx.set_gcn_params(gflat)
-        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
-    w = default_windows(t_total, T, Hf, score) if windows is None else np.asarray(windows, np.int32).reshape(-1)
+    c = _setup("forecast", model, features, edge_index, edge_weight, stats, ctx, windows,
+               lambda t_total, T, Hf: default_windows(t_total, T, Hf, score), prepare_empty=True)
+    w, N, Hf, C = c.entries, c.N, c.Hf, c.C
     if w.size == 0:
         return ForecastResult(None, None, None, None, None, 0, w)
-    ctx.set_tasks([f])
-    mean, std = _stats(stats, C)
-    pred = torch.empty(w.size, N * Hf, C, device=dev) if return_pred else None
-    sums = torch.empty(3, Hf, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
-        ctx.forecast(_capi.stream_ptr(torch), theta, w, batch, scale=std if score else None, pred=pred, skill=sums)
+    pred = torch.empty(w.size, N * Hf, C, device=c.dev) if return_pred else None
+    sums = torch.empty(3, Hf, C, device=c.dev, dtype=torch.float64) if score else None
+    with torch.no_grad(), _score_weights(c.ctx, node_weights if score else None, N):
+        c.ctx.forecast(_capi.stream_ptr(torch), c.theta, w, batch, scale=c.std if score else None, pred=pred,
+                       skill=sums)
         out = None
         if pred is not None:
-            scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
-            shift_t = torch.from_numpy(mean.astype(np.float32)).to(dev)
+            scale_t, shift_t = c.units()
             out = (pred * scale_t + shift_t).view(w.size, Hf, N, C).cpu().numpy()
     if not score:
         return ForecastResult(out, None, None, None, None, int(w.size), w)
@@ -331,45 +358,22 @@ def rollout(model, features, edge_index, stats=None, origins=None, cycles: int =
     import torch
 
     from . import _capi
-    from .model import _set_graph
 
     g = _gap_code(gap)
     R = int(cycles)
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise _capi.SmamlError(-1, "rollout runs on a HIP device only")
-    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
-    f = f.to(dev, torch.float32).contiguous()
-    T = model.base_stgcn.window_size
-    Hf, C = model.forecast_horizon, model.out_channels
-    s = Hf + 1
-    t_total, N = int(f.shape[0]), int(f.shape[1])
-    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
-    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
-    if ew is not None and not torch.is_tensor(ew):
-        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
-    o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
+    c = _setup("rollout", model, features, edge_index, edge_weight, stats, ctx, origins,
+               lambda t_total, T, Hf: rollout_origins(t_total, T, Hf, R, score))
+    o, N, C, s = c.entries, c.N, c.C, c.Hf + 1
     is_gap = (np.arange(R * s) % s) == 0
     gname = "midpoint" if g else "persistence"
     if o.size == 0:
         return RolloutResult(None, is_gap, None, None, None, None, 0, o, R, gname)
-    if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
-    else:
-        dims = model.dims(N)
-        _set_graph(ctx, ei, ew)
-        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
-        ctx.set_gcn_params(gflat)
-        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
-    ctx.set_tasks([f])
-    mean, std = _stats(stats, C)
-    traj = torch.empty(o.size, R, s, N, C, device=dev)
-    sums = torch.empty(3, R * s, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
-        ctx.forecast_rollout(_capi.stream_ptr(torch), theta, o, batch, R, g, scale=std if score else None, traj=traj,
-                             skill=sums)
-        scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
-        shift_t = torch.from_numpy(mean.astype(np.float32)).to(dev)
+    traj = torch.empty(o.size, R, s, N, C, device=c.dev)
+    sums = torch.empty(3, R * s, C, device=c.dev, dtype=torch.float64) if score else None
+    with torch.no_grad(), _score_weights(c.ctx, node_weights if score else None, N):
+        c.ctx.forecast_rollout(_capi.stream_ptr(torch), c.theta, o, batch, R, g, scale=c.std if score else None,
+                               traj=traj, skill=sums)
+        scale_t, shift_t = c.units()
         out = (traj * scale_t + shift_t).view(o.size, R * s, N, C).cpu().numpy()
     if not score:
         return RolloutResult(out, is_gap, None, None, None, None, int(o.size), o, R, gname)
@@ -471,46 +475,25 @@ def ensemble_forecast(model, features, edge_index, stats=None, members: int = 16
 
     from . import _capi
     from .hybrid_model import draw_dropout_seed
-    from .model import _set_graph
 
-    dev = next(model.parameters()).device
-    if ctx is None and dev.type != "cuda":
-        raise _capi.SmamlError(-1, "ensemble_forecast runs on a HIP device only")
+    # (a caller's context may live elsewhere than the model: only the model's own needs the device)
+    c = _setup("ensemble_forecast", model, features, edge_index, edge_weight, stats, ctx, windows,
+               lambda t_total, T, Hf: default_windows(t_total, T, Hf, score), device_only=ctx is None)
     p_gcn = float(model.base_stgcn.dropout.p) if p_gcn is None else float(p_gcn)
     p_lstm = float(model.dropout.p) if p_lstm is None else float(p_lstm)
     seed = draw_dropout_seed() if seed is None else int(seed) & 0xFFFFFFFF
     E = int(members)
-    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
-    f = f.to(dev, torch.float32).contiguous()
-    T = model.base_stgcn.window_size
-    Hf, C = model.forecast_horizon, model.out_channels
-    t_total, N = int(f.shape[0]), int(f.shape[1])
-    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
-    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
-    if ew is not None and not torch.is_tensor(ew):
-        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
-    w = default_windows(t_total, T, Hf, score) if windows is None else np.asarray(windows, np.int32).reshape(-1)
+    w, N, Hf, C, dev = c.entries, c.N, c.Hf, c.C, c.dev
     if w.size == 0:
         return EnsembleResult(None, None, None, None, None, None, None, None, 0, E, w, seed, p_gcn, p_lstm)
-    if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
-    else:
-        dims = model.dims(N)
-        _set_graph(ctx, ei, ew)
-        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
-        ctx.set_gcn_params(gflat)
-        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
-    ctx.set_tasks([f])
-    mean_s, std = _stats(stats, C)
     mean = torch.empty(w.size, N * Hf, C, device=dev)
     spread = torch.empty(w.size, N * Hf, C, device=dev)
     mem = torch.empty(E, w.size, N * Hf, C, device=dev) if return_members else None
     sums = torch.empty(4, Hf, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
-        ctx.forecast_ensemble(_capi.stream_ptr(torch), theta, w, batch, E, p_gcn, p_lstm, seed,
-                              scale=std if score else None, mean=mean, spread=spread, member_pred=mem, scores=sums)
-        scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
-        shift_t = torch.from_numpy(mean_s.astype(np.float32)).to(dev)
+    with torch.no_grad(), _score_weights(c.ctx, node_weights if score else None, N):
+        c.ctx.forecast_ensemble(_capi.stream_ptr(torch), c.theta, w, batch, E, p_gcn, p_lstm, seed,
+                                scale=c.std if score else None, mean=mean, spread=spread, member_pred=mem, scores=sums)
+        scale_t, shift_t = c.units()
         mean_o = (mean * scale_t + shift_t).view(w.size, Hf, N, C).cpu().numpy()
         spread_o = (spread * scale_t).view(w.size, Hf, N, C).cpu().numpy()
         mem_o = (mem * scale_t + shift_t).view(E, w.size, Hf, N, C).cpu().numpy() if mem is not None else None
@@ -613,52 +596,29 @@ def ensemble_rollout(model, features, edge_index, stats=None, origins=None, cycl
 
     from . import _capi
     from .hybrid_model import draw_dropout_seed
-    from .model import _set_graph
 
     g = _gap_code(gap)
     R, E = int(cycles), int(members)
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise _capi.SmamlError(-1, "ensemble_rollout runs on a HIP device only")
+    c = _setup("ensemble_rollout", model, features, edge_index, edge_weight, stats, ctx, origins,
+               lambda t_total, T, Hf: rollout_origins(t_total, T, Hf, R, score))
     p_gcn = float(model.base_stgcn.dropout.p) if p_gcn is None else float(p_gcn)
     p_lstm = float(model.dropout.p) if p_lstm is None else float(p_lstm)
     seed = draw_dropout_seed() if seed is None else int(seed) & 0xFFFFFFFF
-    f = features if torch.is_tensor(features) else torch.from_numpy(np.ascontiguousarray(features))
-    f = f.to(dev, torch.float32).contiguous()
-    T = model.base_stgcn.window_size
-    Hf, C = model.forecast_horizon, model.out_channels
-    s = Hf + 1
-    t_total, N = int(f.shape[0]), int(f.shape[1])
-    ei = edge_index if torch.is_tensor(edge_index) else torch.from_numpy(np.asarray(edge_index))
-    ew = edge_weight  # (optional: a weighted graph, or an in-degree above 7, runs in the library's CSR form)
-    if ew is not None and not torch.is_tensor(ew):
-        ew = torch.from_numpy(np.asarray(ew, dtype=np.float32))
-    o = rollout_origins(t_total, T, Hf, R, score) if origins is None else np.asarray(origins, np.int32).reshape(-1)
+    o, N, C, dev, s = c.entries, c.N, c.C, c.dev, c.Hf + 1
     is_gap = (np.arange(R * s) % s) == 0
     gname = "midpoint" if g else "persistence"
     tail = (int(o.size), E, o, R, gname, seed, p_gcn, p_lstm)
     if o.size == 0:
         return EnsembleRolloutResult(None, None, None, is_gap, None, None, None, None, None, None, *tail)
-    if ctx is None:
-        ctx, dims, theta = model._prepare(f[:T].reshape(T * N, -1), ei, ew)
-    else:
-        dims = model.dims(N)
-        _set_graph(ctx, ei, ew)
-        gflat, _ = model._packed(1, model._gcn_params(), dims, dev)
-        ctx.set_gcn_params(gflat)
-        theta, _ = model._packed(0, model._trainable_params(), dims, dev)
-    ctx.set_tasks([f])
-    mean_s, std = _stats(stats, C)
     mean = torch.empty(o.size, R, s, N, C, device=dev)
     spread = torch.empty(o.size, R, s, N, C, device=dev)
     mem = torch.empty(E, o.size, R, s, N, C, device=dev) if return_members else None
     sums = torch.empty(4, R * s, C, device=dev, dtype=torch.float64) if score else None
-    with torch.no_grad(), _score_weights(ctx, node_weights if score else None, N):
-        ctx.forecast_rollout_ensemble(_capi.stream_ptr(torch), theta, o, batch, R, E, p_gcn, p_lstm, seed, gap=g,
-                                      scale=std if score else None, member_traj=mem, mean=mean, spread=spread,
-                                      scores=sums)
-        scale_t = torch.from_numpy(std.astype(np.float32)).to(dev)
-        shift_t = torch.from_numpy(mean_s.astype(np.float32)).to(dev)
+    with torch.no_grad(), _score_weights(c.ctx, node_weights if score else None, N):
+        c.ctx.forecast_rollout_ensemble(_capi.stream_ptr(torch), c.theta, o, batch, R, E, p_gcn, p_lstm, seed, gap=g,
+                                        scale=c.std if score else None, member_traj=mem, mean=mean, spread=spread,
+                                        scores=sums)
+        scale_t, shift_t = c.units()
         mean_o = (mean * scale_t + shift_t).view(o.size, R * s, N, C).cpu().numpy()
         spread_o = (spread * scale_t).view(o.size, R * s, N, C).cpu().numpy()
         mem_o = (mem * scale_t + shift_t).view(E, o.size, R * s, N, C).cpu().numpy() if mem is not None else None
