@@ -165,6 +165,15 @@ int smaml_loss_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t
 /* Frozen GCN parameters (flat, layout which=1), device pointer kept by reference. */
 int smaml_set_gcn_params(smaml_ctx* ctx, const float* gcn_flat);
 
+/* The meta-step's per-stream GCN feature cache (option "gcn_stream_cache", default 1): with the frozen base and
+ * no GCN dropout, smaml_meta_step computes the features of each stream row once and keeps them, per stream
+ * (keyed by its device pointer and length), across inner steps, meta-steps and smaml_set_tasks calls.
+ * smaml_set_gcn_params and smaml_set_graph[_weighted] forget the cached rows themselves. A caller who CHANGES
+ * WHAT A REGISTERED STREAM'S MEMORY HOLDS -- writes it in place, or frees it and lets another stream of the same
+ * length take its address -- must call this before the next smaml_meta_step: the cached rows are forgotten, the
+ * tables stay allocated. Option "gcn_stream_cache_mb": cap on the tables' bytes (-1, the default: free HBM only). */
+int smaml_gcn_cache_invalidate(smaml_ctx* ctx);
+
 /* Size the workspace for `tasks` x `batch` samples per step (grows, never shrinks). */
 int smaml_reserve(smaml_ctx* ctx, int32_t tasks, int32_t batch);
 
@@ -650,8 +659,10 @@ int smaml_timing_collect(smaml_ctx* ctx, double* ms, double* flops, int64_t* cou
  * kernels.h enum Variant (_capi.VARIANTS): fwd, fwd_drop, fwd_split, fwd_img, fwd_dual,
  * fwd_dual_kept, fwd_dual_img, bwd_big, bwd_small, bwd_split, bwd_dual_big, bwd_dual_big_kept,
  * bwd_dual_small, bwd_dual_small_kept, wgrad, wgrad_wide, wgrad_pair, fwd_kw, bwd_kw, gcn_dedup,
- * xg_dedup, wgrad_dedup, f_compact, fwd_infer (smaml_forecast's inference step), fwd_infer_drop
- * (smaml_forecast_ensemble's: one launch per diagonal and member group).
+ * xg_dedup, wgrad_dedup, f_compact, gcn_cache (forwards of smaml_meta_step whose GCN features came from the
+ * per-stream cache), gcn_cache_rows (stream rows that cache computed: rows, not launches), fwd_infer
+ * (smaml_forecast's inference step), fwd_infer_drop (smaml_forecast_ensemble's: one launch per diagonal and
+ * member group).
  * Writes min(cap, count) entries, *count = number of variants; reset != 0 zeroes them. Host-side
  * counters: no synchronisation. Lets tests assert which configurations ran. */
 int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count, int32_t reset);
@@ -755,6 +766,14 @@ int smaml_variant_counts(smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* 
  *                                  stream rows (xg_dedup forwards on the big tiles, wgrad_dedup
  *                                  backwards), the GCN stores each distinct row once instead of to every
  *                                  (sample, step) holding it (1, the default; bitwise equal to 0).
+ *   "gcn_stream_cache":            smaml_meta_step computes the frozen base's features once per stream row
+ *                                  and keeps them across inner steps, meta-steps and smaml_set_tasks calls
+ *                                  (smaml_gcn_cache_invalidate; 1, the default; bitwise equal to 0);
+ *   "gcn_stream_cache_mb":         cap on that cache's bytes in MiB (-1, the default: whatever free HBM
+ *                                  allows; 0: no stream gets tables);
+ *   "so_f_store":                  0: a second-order meta-step keeps no per-step copy of its GCN features
+ *                                  (the sweep asks for them again); 1, the default: best effort, and none
+ *                                  where the per-stream cache serves every inner step.
  *   (Round 6 removed the options of arms that measured slower -- bptt_push, wgrad_ws, rowsum_side,
  *   gcn_side, reduce_side, wgrad_overlap, wgrad_min_kt, wgrad_threads, and its own h_img; DESIGN.md
  *   keeps their A/B record.) */

@@ -20,7 +20,7 @@ import sys
 
 # bench.py timing categories (api.cpp TIMED(...)) -> the kernels each category launches
 CATEGORIES = {
-    "gcn_layer": r"k_gcn_layer|k_gcn_mlp|k_gcn_expand|k_gcn_compact",
+    "gcn_layer": r"k_gcn_layer|k_gcn_mlp|k_gcn_expand|k_gcn_compact|k_gcn_cache_gather",
     "lstm_fwd_step": r"k_lstm_fwd_step",
     "lstm_fwd_dual": r"k_lstm_fwd_dual",
     "lstm_bwd_step": r"k_lstm_bwd_step",

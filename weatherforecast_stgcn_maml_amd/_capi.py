@@ -29,7 +29,7 @@ EXPORTS = (
     "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
     "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats", "smaml_graph_csr", "smaml_set_graph_weighted",
     "smaml_graph_stats", "smaml_loss_weights_check", "smaml_set_loss_weights", "smaml_set_score_weights",
-    "smaml_loss_stats",
+    "smaml_loss_stats", "smaml_gcn_cache_invalidate",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -37,7 +37,8 @@ GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
 # kernels.h enum Variant: launch counters per kernel tile configuration (smaml_variant_counts)
 VARIANTS = ("fwd", "fwd_drop", "fwd_split", "fwd_img", "fwd_dual", "fwd_dual_kept", "fwd_dual_img", "bwd_big", "bwd_small", "bwd_split",
             "bwd_dual_big", "bwd_dual_big_kept", "bwd_dual_small", "bwd_dual_small_kept", "wgrad", "wgrad_wide", "wgrad_pair",
-            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact", "fwd_infer", "fwd_infer_drop")
+            "fwd_kw", "bwd_kw", "gcn_dedup", "xg_dedup", "wgrad_dedup", "f_compact", "gcn_cache", "gcn_cache_rows",
+            "fwd_infer", "fwd_infer_drop")
 
 # api.cpp enum Cat: one kernel per category (the bench's roofline kernel is one symbol)
 TIMING_CATEGORIES = ("gcn_layer", "lstm_fwd_step", "lstm_fwd_dual", "head_loss", "head_dh", "lstm_bwd_step",
@@ -116,6 +117,7 @@ _SIGS = {
                               PI64, I32], I32),
     "smaml_variant_counts": ([P, PI64, I32, PI32, I32], I32),
     "smaml_set_option": ([P, ctypes.c_char_p, I64], I32),
+    "smaml_gcn_cache_invalidate": ([P], I32),
     "smaml_dropout": ([P, P, P, I64, F32, ctypes.c_uint32, I32], I32),
     "smaml_sync": ([P, P], I32),
     "smaml_gcn_conv_ex": ([P, P, P, I32, I32, P, P, I32, I32, P], I32),
@@ -440,7 +442,21 @@ class Context:
         arr = (P * len(feats))(*[ptr(f) for f in feats])
         tt = (ctypes.c_int32 * len(feats))(*[int(f.shape[0]) for f in feats])
         self._tasks = list(feats)
+        # The per-stream GCN feature cache is keyed by stream address: a stream stays referenced here for as long
+        # as the context may hold rows of it, so its memory cannot pass to another tensor in the meantime.
+        pin = getattr(self, "_gc_pin", None)
+        if pin is None or len(pin) > 256:
+            if pin is not None:
+                self.gcn_cache_invalidate()
+            pin = self._gc_pin = {}
+        for f in feats:
+            pin[ptr(f)] = f
         check(self._L.smaml_set_tasks(self._h, len(feats), arr, tt))
+
+    def gcn_cache_invalidate(self):
+        """Forget the cached GCN features of every stream (smaml_gcn_cache_invalidate): after writing a registered
+        stream's tensor in place."""
+        check(self._L.smaml_gcn_cache_invalidate(self._h))
 
     def meta_step(self, stream, theta, order, steps, batch, windows: np.ndarray, inner_lr, max_norm,
                   query_scale, meta_grad=None, losses=None, norms=None, fast_out=None):

@@ -13,6 +13,7 @@
 #include <dlfcn.h>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -415,6 +416,7 @@ struct smaml_ctx {
   float *so_u = nullptr, *so_hu = nullptr;
   HipBuf so_theta, so_grad, so_norm, so_coef;  // float; all four set or none (ensure_so_store)
   HipBuf so_F;  // float [K][Z][T][M][Hc] GCN features of every inner step (empty: recompute)
+  int so_f_store = 1;  // smaml_set_option("so_f_store"): 0 = never keep them (the sweep asks run_gcn again)
   std::vector<int8_t> so_fc;  // per inner step: whether run_gcn wrote its so_F slot compact (Work::fcompact)
   float* F_main = nullptr;  // the workspace's own F buffer
   // batch-1 adaptation: GCN features per window of task 0 (the frozen GCN stack without dropout
@@ -444,6 +446,33 @@ struct smaml_ctx {
   int ad_gcn_batch = 32;           // windows per GCN pass when filling the cache (<= 1: one per step)
   int ad_phase_sync = 0;           // smaml_set_option("adapt_phase_sync"): sync at the phase boundaries
   AdPhases ad_ph;                  // host-timed phases of the last smaml_adapt_steps (smaml_adapt_phases)
+  // Per-stream GCN feature cache of the meta-step (smaml_set_option("gcn_stream_cache")): the frozen base without
+  // GCN dropout gives stream row r of a task the same features in every window, inner step and meta-step (F2, F3),
+  // so each row is computed once -- as a window's t = 0 row (graph gather, table t0) and as a t >= 1 row (no
+  // neighbours, table t1) -- and consecutive-window steps gather their F from the tables (run_gcn_cached).
+  // Keyed by stream pointer and length: entries survive smaml_set_tasks (task groups rotate every meta-step).
+  struct GcEntry {
+    const float* key = nullptr;
+    int t_total = 0;
+    HipBuf tab;                   // float [2][t_total][N][Hc]: t0, then t1
+    std::vector<uint8_t> f0, f1;  // per stream row: filled (host; the fills are enqueued, gc_ev behind them)
+    int64_t last_set = 0;         // gc_gen of the last meta-step that used the entry
+  };
+  std::vector<std::unique_ptr<GcEntry>> gc;
+  int gc_on = 1;                // smaml_set_option("gcn_stream_cache")
+  int64_t gc_budget_mb = -1;    // smaml_set_option("gcn_stream_cache_mb"): cap on the tables' bytes (-1: free HBM only)
+  int64_t gc_gen = 0;           // meta-steps that asked for the cache
+  hipStream_t gc_stream = nullptr;  // the stream the last fills were enqueued on (compared, never used)
+  hipEvent_t gc_ev = nullptr;       // recorded behind them
+  bool gc_ev_set = false;
+  HipBuf gc_ptrs;               // device pointer table of a fill's t >= 1 runs
+  // the running step's view of the cache (meta-step only; tab null: run_gcn computes the features itself)
+  struct GcStep {
+    const float* const* tab = nullptr;  // device [Z][2] (launch_gcn_cache_gather)
+    GcEntry* const* ent = nullptr;      // host [Z]
+    const int32_t* w0 = nullptr;        // host [Z]: each task's first window
+    bool sweep = false;                 // the second-order sweep's visit of a step the inner loop ran
+  } gc_cur;
   float *Hs_main = nullptr, *Cs_main = nullptr, *Gs_main = nullptr;  // the workspace's own activations
   // primal of the last inner steps kept for the second-order sweep (ensure_keep): slot 0 adds
   // dG + dh to the workspace's Hs/Cs/Gs, slot i >= 1 holds Hs/Cs/Gs/dG/dh of its own
@@ -550,6 +579,70 @@ void ad_cache_drop(smaml_ctx* c) {
   c->ad.clear();  // (each slot's buffer is released after a device sync, devbuf.h)
 }
 
+// Free HBM the per-stream GCN feature cache leaves (after the kept slots took theirs), and how many meta-steps
+// an entry may go unused before a stream that finds no room may take its place.
+constexpr int64_t GC_MARGIN = 2ll << 30, GC_STALE = 64;
+
+// Drops the per-stream GCN feature cache, tables and all.
+void gc_drop(smaml_ctx* c) {
+  c->gc.clear();
+  c->gc_cur = {};
+}
+
+// New graph / GCN parameters / a stream rewritten in place: every cached row is stale; the tables stay allocated.
+void gc_invalidate(smaml_ctx* c) {
+  for (auto& e : c->gc) {
+    std::fill(e->f0.begin(), e->f0.end(), (uint8_t)0);
+    std::fill(e->f1.begin(), e->f1.end(), (uint8_t)0);
+  }
+}
+
+// The cache entries of the registered tasks, ent [Z] (null: that stream has none), allocating best effort the
+// tables of streams seen for the first time. Whether every task has one.
+bool gc_prepare(smaml_ctx* c, int Z, std::vector<smaml_ctx::GcEntry*>& ent) {
+  const Dims& d = c->d;
+  ++c->gc_gen;
+  ent.assign((size_t)Z, nullptr);
+  int64_t held = 0;
+  for (auto& e : c->gc) held += e->tab.cap;
+  bool all = true;
+  for (int z = 0; z < Z; ++z) {
+    smaml_ctx::GcEntry* hit = nullptr;
+    for (auto& e : c->gc)
+      if (e->key == c->feats[z] && e->t_total == c->t_total[z]) hit = e.get();
+    if (!hit) {
+      const int64_t bytes = 2ll * c->t_total[z] * d.N * d.Hc * 4;
+      auto fits = [&]() { return c->gc_budget_mb < 0 || held + bytes <= (c->gc_budget_mb << 20); };
+      auto e = std::make_unique<smaml_ctx::GcEntry>();
+      bool ok = fits() && e->tab.grow_if_room(bytes, GC_MARGIN);
+      while (!ok) {  // no room: the stream no meta-step has used for longest gives its tables up, if long enough
+        size_t old = c->gc.size();
+        for (size_t i = 0; i < c->gc.size(); ++i)
+          if (c->gc[i]->last_set + GC_STALE < c->gc_gen && (old == c->gc.size() || c->gc[i]->last_set < c->gc[old]->last_set))
+            old = i;
+        if (old == c->gc.size()) break;
+        held -= c->gc[old]->tab.cap;
+        c->gc.erase(c->gc.begin() + (std::ptrdiff_t)old);
+        ok = fits() && e->tab.grow_if_room(bytes, GC_MARGIN);
+      }
+      if (!ok) {
+        all = false;
+        continue;
+      }
+      e->key = c->feats[z];
+      e->t_total = c->t_total[z];
+      e->f0.assign((size_t)e->t_total, 0);
+      e->f1.assign((size_t)e->t_total, 0);
+      held += bytes;
+      hit = e.get();
+      c->gc.push_back(std::move(e));
+    }
+    hit->last_set = c->gc_gen;
+    ent[z] = hit;
+  }
+  return all;
+}
+
 int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
   const int zb = Z * B;
   // per-task activation slabs are addressed with 32-bit offsets inside the kernels
@@ -558,6 +651,7 @@ int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
   so = so || c->so_cap;
   if (zb <= c->zb_cap && Z <= c->z_cap && so == c->so_cap) return SMAML_OK;
   ad_cache_drop(c);  // a growing workspace takes precedence over the adaptation feature cache
+  gc_drop(c);        // ... and over the meta-step's per-stream one
   const int zbc = std::max(zb, c->zb_cap), zc = std::max(Z, c->z_cap);
   const Dims& d = c->d;
   const int64_t rows = (int64_t)zbc * d.T * d.N;
@@ -639,10 +733,16 @@ int reserve(smaml_ctx* c, int Z, int B, bool so = false) {
 
 // Per-step stores of the second-order sweep: theta_k and g_k [K][Z][P], |g_k| and the
 // clip coefficient [K][Z].
-int ensure_so_store(smaml_ctx* c, int K, int Z, int B) {
+int ensure_so_store(smaml_ctx* c, int K, int Z, int B, bool cached) {
   // GCN features of each inner step, kept for the second-order sweep (weight-independent, F2).
-  // Best effort: without room the sweep recomputes them.
-  (void)c->so_F.grow_if_room((int64_t)K * Z * B * c->d.T * c->d.N * c->d.Hc * 4, SO_F_MARGIN);
+  // Best effort: without room the sweep recomputes them. cached: every inner step of this meta-step is served
+  // from the per-stream GCN feature cache, which serves the sweep too -- no store is made for it (one that is
+  // already there and large enough is used: it costs nothing more).
+  const int64_t fbytes = (int64_t)K * Z * B * c->d.T * c->d.N * c->d.Hc * 4;
+  if (c->so_f_store && (!cached || c->so_F.cap >= fbytes))
+    (void)c->so_F.grow_if_room(fbytes, SO_F_MARGIN);
+  else
+    (void)c->so_F.release();
   const int64_t nc = (int64_t)K * Z * 4, need = nc * c->po.P;
   HIP_TRY(grow_all<HipAlloc>({{&c->so_theta, need}, {&c->so_grad, need}, {&c->so_norm, nc}, {&c->so_coef, nc}}));
   return SMAML_OK;
@@ -653,10 +753,11 @@ int ensure_so_store(smaml_ctx* c, int K, int Z, int B) {
 // BPTT GEMMs). Slot 0 (step K-1) keeps the workspace's own Hs/Cs/Gs -- the query then runs in
 // the tangent buffers -- and adds dG + dh; slot i >= 1 (step K-1-i) holds its own
 // Hs/Cs/Gs/dG/dh. Best effort: as many slots as fit in free HBM with a margin, capped by the
-// SMAML_KEEP environment variable (0 disables). Needs the GCN feature cache (so_F).
-int ensure_keep(smaml_ctx* c, int K, int Z, int B) {
+// SMAML_KEEP environment variable (0 disables). Needs the steps' GCN features at hand: the per-step store
+// (so_F) or, `cached`, the per-stream GCN feature cache.
+int ensure_keep(smaml_ctx* c, int K, int Z, int B, bool cached) {
   const Dims& d = c->d;
-  int want = c->so_F.ptr ? K : 0;
+  int want = c->so_F.ptr || cached ? K : 0;
   if (c->keep_max >= 0)
     want = std::min(want, c->keep_max);
   else if (const char* e = std::getenv("SMAML_KEEP"))
@@ -954,6 +1055,110 @@ bool f_compact_ok(smaml_ctx* c, bool consec) {
   return xgd_scratch(c, 2 * xg_dedup_rows(w.B, d.T, d.N) * 4 * d.H * w.Z) != nullptr;
 }
 
+// A consecutive-window step served from the per-stream GCN feature cache (c->gc_cur): the rows the step reads
+// that the tables do not hold yet -- w0 .. w0 + B - 1 of t0, w0 + 1 .. w0 + B + T - 2 of t1 -- are computed in
+// runs of consecutive stream rows by run_gcn's own kernels (a row's arithmetic does not depend on which rows share
+// its launch: the t = 0 rows as N-row samples with the graph gather, layer by layer; the others by k_gcn_mlp's row-
+// run form, or on the per-layer path as one pseudo-sample without neighbours), then one copy kernel lays F out
+// as run_gcn would have (w.fcompact decided by the caller). Once a stream's rows are filled no GCN kernel runs.
+int run_gcn_cached(smaml_ctx* c, hipStream_t s) {
+  const Dims& d = c->d;
+  Work& w = c->w;
+  const smaml_ctx::GcStep& g = c->gc_cur;
+  // the filled flags speak of work enqueued on the last fill's stream: another stream waits for it
+  if (c->gc_ev_set && c->gc_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->gc_ev, 0));
+  struct Run {
+    smaml_ctx::GcEntry* e;
+    int a, n;  // stream rows a .. a + n - 1
+  };
+  std::vector<Run> r0, r1;
+  auto missing = [](smaml_ctx::GcEntry* e, std::vector<uint8_t>& f, int lo, int hi, std::vector<Run>& out) {
+    for (int r = lo; r < hi; ++r) {
+      if (f[(size_t)r]) continue;
+      f[(size_t)r] = 1;
+      if (!out.empty() && out.back().e == e && out.back().a + out.back().n == r)
+        ++out.back().n;
+      else
+        out.push_back({e, r, 1});
+    }
+  };
+  struct Guard {  // an error below leaves rows marked that were never enqueued: forget them all
+    smaml_ctx* c;
+    bool done = false;
+    ~Guard() {
+      if (!done) gc_invalidate(c);
+    }
+  } guard{c};
+  for (int z = 0; z < w.Z; ++z) {
+    missing(g.ent[z], g.ent[z]->f0, g.w0[z], g.w0[z] + w.B, r0);
+    if (d.T > 1) missing(g.ent[z], g.ent[z]->f1, g.w0[z] + 1, g.w0[z] + w.B + d.T - 1, r1);
+  }
+  const int64_t blk = (int64_t)d.N * d.Hc, xblk = (int64_t)d.N * d.Cin0;
+  float* bufs[2] = {w.gcnA, w.gcnB};  // a run is at most B + T - 2 rows: within the step's own [Z B T N][Hc]
+  const GraphView gv = graph_view(c);
+  const bool fused = gcn_mlp_supported(d) && c->kn.gcn_fused;
+  if (!r1.empty()) {
+    std::vector<const float*> ptrs;
+    for (const Run& r : r1) ptrs.push_back(r.e->key + (int64_t)r.a * xblk);
+    HIP_TRY(c->gc_ptrs.grow(std::max<int64_t>((int64_t)ptrs.size(), 256) * (int64_t)sizeof(float*)));
+    TRY(c->stage.upload(s, c->gc_ptrs.ptr, ptrs.data(), (int64_t)ptrs.size() * (int64_t)sizeof(float*)));
+    const float* const* tab = c->gc_ptrs.as<const float*>();
+    GcnWOff wo;
+    for (int k = 0; k < 4; ++k) {
+      wo.w[k] = c->go.w[k];
+      wo.b[k] = c->go.b[k];
+    }
+    char* wimg = nullptr;
+    if (fused) {
+      HIP_TRY(c->gcn_wimg.grow(gcn_wimg_bytes(d)));
+      wimg = c->gcn_wimg.as<char>();
+      TIMED(c, s, C_MISC, 0, launch_gcn_wsplit(s, d, c->gcn, wo, wimg));
+    }
+    for (size_t i = 0; i < r1.size(); ++i) {
+      const Run& r = r1[i];
+      float* out = r.e->tab.as<float>() + ((int64_t)r.e->t_total + r.a) * blk;
+      if (fused) {
+        TIMED(c, s, C_GCN, 2.0 * r.n * d.N * d.Hc * (d.Cin0 + 3.0 * d.Hc),
+              launch_gcn_mlp_run(s, d, 1, r.n, tab + i, c->gcn, wo, wimg, out));
+        continue;
+      }
+      const float* src = nullptr;
+      for (int k = 0; k < 4; ++k) {
+        float* dst = k == 3 ? out : bufs[k & 1];
+        TIMED(c, s, C_GCN, 2.0 * r.n * d.N * c->go.cin[k] * d.Hc,
+              launch_gcn_layer(s, d, k, 1, 1, k == 0 ? tab + i : nullptr, src, dst, false, true, c->gcn + c->go.w[k],
+                               c->gcn + c->go.b[k], c->go.cin[k], d.Hc, gv, r.n * d.N, 0, nullptr));
+        src = dst;
+      }
+    }
+  }
+  for (const Run& r : r0) {  // t = 0 rows: r.n samples of N rows, one after another in the stream and in t0
+    const float* src = r.e->key + (int64_t)r.a * xblk;
+    for (int k = 0; k < 4; ++k) {
+      float* dst = k == 3 ? r.e->tab.as<float>() + (int64_t)r.a * blk : bufs[k & 1];
+      TIMED(c, s, C_GCN, 2.0 * r.n * d.N * c->go.cin[k] * d.Hc,
+            launch_gcn_layer(s, d, k, r.n, 1, nullptr, src, dst, false, true, c->gcn + c->go.w[k], c->gcn + c->go.b[k],
+                             c->go.cin[k], d.Hc, gv, d.N, d.N, nullptr));
+      src = dst;
+    }
+  }
+  int64_t rows = 0;
+  for (const Run& r : r0) rows += r.n;
+  for (const Run& r : r1) rows += r.n;
+  if (w.vcount) w.vcount[V_GCN_CACHE_ROWS] += rows;
+  if (rows > 0 || c->gc_stream != s) {
+    if (!c->gc_ev) HIP_TRY(hipEventCreateWithFlags(&c->gc_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->gc_ev, s));
+    c->gc_ev_set = true;
+    c->gc_stream = s;
+  }
+  count_variant(w, V_GCN_CACHE);
+  TIMED(c, s, C_MISC, 0, launch_gcn_cache_gather(s, d, w.Z, w.B, g.tab, w.F, w.fcompact != 0));
+  HIP_TRY(hipGetLastError());
+  guard.done = true;
+  return SMAML_OK;
+}
+
 // GCN x4 (no_grad, F2): sample windows -> w.F [Z][T][M][Hc]. With the fused kernel (Hc = 256): the
 // rows t >= 1 (no neighbours, F3) run all four convs in one launch (k_gcn_mlp, activations kept in
 // registers), the t = 0 rows (ELL gather) four per-layer launches over N-row blocks.
@@ -969,7 +1174,15 @@ int run_gcn(smaml_ctx* c, hipStream_t s, const float* const* xtab_dev, const flo
   const Dims& d = c->d;
   Work& w = c->w;
   w.fcompact = fcompact >= 0 ? fcompact : f_compact_ok(c, consec) ? 1 : 0;
-  if (w.fcompact) count_variant(w, V_F_COMPACT);
+  const bool served = consec && c->gc_cur.tab && fcompact < 0 && c->kn.gcn_dedup && w.B > 1 && !w.drop.gcn();
+  // (a sweep step served from the cache lays the same step's features out again: counted once per step, as when
+  // the sweep read them from the per-step store)
+  const bool revisit = served && c->gc_cur.sweep;
+  if (w.fcompact && !revisit) count_variant(w, V_F_COMPACT);
+  if (served) {
+    if (!revisit) count_variant(w, V_GCN_DEDUP);  // (each distinct stream row at most once, here once per stream)
+    return run_gcn_cached(c, s);
+  }
   const int rps = d.T * d.N;
   const int zb = w.Z * w.B;
   const float* src = nullptr;
@@ -2423,6 +2636,7 @@ int smaml_destroy(smaml_ctx* c) {
     if (c->join_ev[i]) (void)hipEventDestroy(c->join_ev[i]);
   }
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+  if (c->gc_ev) (void)hipEventDestroy(c->gc_ev);
   if (c->bar_err_host) (void)hipHostFree(c->bar_err_host);
   for (auto& r : c->tm.recs) {
     (void)hipEventDestroy(r.a);
@@ -2459,6 +2673,7 @@ int smaml_set_graph(smaml_ctx* c, const int64_t* edge_index_host, int64_t num_ed
   std::vector<float> vals;
   TRY(build_ell(edge_index_host, num_edges, c->d.N, cols, vals));
   ad_cache_invalidate(c);
+  gc_invalidate(c);
   const int N = c->d.N;
   std::vector<int32_t> rp, rc, tp, tc;
   std::vector<float> rv, tv;
@@ -2503,6 +2718,7 @@ int smaml_set_graph_weighted(smaml_ctx* c, const int64_t* edge_index_host, const
   std::vector<float> rv, tv;
   TRY(build_csr(edge_index_host, edge_weight_host, num_edges, N, rp, rc, rv));
   ad_cache_invalidate(c);
+  gc_invalidate(c);
   csr_transpose(N, rp, rc, rv, tp, tc, tv);
   const int64_t nnz = std::max<int64_t>((int64_t)rc.size(), 1) * 4, np = (int64_t)rp.size() * 4;
   HIP_TRY(grow_all<HipAlloc>(
@@ -2589,6 +2805,13 @@ int smaml_set_gcn_params(smaml_ctx* c, const float* gcn_flat) {
   if (!aligned16(gcn_flat)) return fail(SMAML_EINVAL, "gcn params must be 16-byte aligned");
   c->gcn = gcn_flat;
   ad_cache_invalidate(c);  // cached features belong to the previous GCN parameters (the slots stay allocated)
+  gc_invalidate(c);     // (parameters may be rewritten in place behind a kept pointer: the call is the signal)
+  return SMAML_OK;
+}
+
+int smaml_gcn_cache_invalidate(smaml_ctx* c) {
+  if (!c) return fail(SMAML_EINVAL, "ctx is NULL");
+  gc_invalidate(c);
   return SMAML_OK;
 }
 
@@ -2946,12 +3169,6 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   TRY(ensure_bar(c));
   TRY(check_device_error(c));
   TRY(reserve(c, Z, B, order == 2));
-  if (order == 2) TRY(ensure_so_store(c, std::max(steps, 1), Z, B));
-  if (order == 2) TRY(ensure_keep(c, steps, Z, B));
-  set_work(c, Z, B);
-  use_loss_weights(c, nullptr);  // task z reads set z
-  const int nkeep = order == 2 ? std::min(std::min(c->keep_n, c->keep_want), steps) : 0;
-  c->keep_last = nkeep;
   // sample window table for every step (support steps then the query batch)
   const int64_t nptr = (int64_t)(steps + 1) * Z * B;
   // (+ each step's per-task first-window pointers, the GCN's consecutive-window tables)
@@ -2977,13 +3194,53 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     for (int z = 0; z < Z; ++z) ptrs[nptr + (int64_t)k * Z + z] = ptrs[((int64_t)k * Z + z) * B];
     is_consec[k] = ok;
   }
+  // The per-stream GCN feature cache serves the consecutive-window steps when every task of the group has its
+  // tables (gc_prepare; they do not move before this call returns): behind the tables above, per such step and
+  // task, where its first window starts in t0 and one stream row later in t1 (launch_gcn_cache_gather).
+  std::vector<smaml_ctx::GcEntry*> gc_ent;
+  std::vector<int32_t> gc_w0((size_t)(steps + 1) * Z, 0);
+  struct GcScope {  // the step views point into this call's vectors
+    smaml_ctx* c;
+    ~GcScope() { c->gc_cur = {}; }
+  } gc_scope{c};
+  const bool any_consec = std::find(is_consec.begin(), is_consec.end(), (char)1) != is_consec.end();
+  const bool gc_use = c->gc_on && c->kn.gcn_dedup && c->p_gcn == 0.f && any_consec && gc_prepare(c, Z, gc_ent);
+  const int64_t gc_base = (int64_t)ptrs.size();
+  if (gc_use) {
+    ptrs.resize((size_t)gc_base + (size_t)(steps + 1) * Z * 2, nullptr);
+    const int64_t blk = (int64_t)d.N * d.Hc;
+    for (int k = 0; k <= steps; ++k)
+      for (int z = 0; z < Z && is_consec[k]; ++z) {
+        const int32_t w0 = windows_host[((int64_t)k * Z + z) * B];
+        const float* t0 = gc_ent[z]->tab.as<float>();
+        gc_w0[(size_t)k * Z + z] = w0;
+        ptrs[gc_base + ((int64_t)k * Z + z) * 2] = t0 + (int64_t)w0 * blk;
+        ptrs[gc_base + ((int64_t)k * Z + z) * 2 + 1] = t0 + ((int64_t)gc_ent[z]->t_total + w0 + 1) * blk;
+      }
+  }
+  // every support step served from the cache: the sweep takes its features there too, no per-step store
+  const bool so_cached = gc_use && std::find(is_consec.begin(), is_consec.begin() + steps, (char)0) == is_consec.begin() + steps;
+  if (order == 2) TRY(ensure_so_store(c, std::max(steps, 1), Z, B, so_cached));
+  if (order == 2) TRY(ensure_keep(c, steps, Z, B, so_cached));
+  set_work(c, Z, B);
+  use_loss_weights(c, nullptr);  // task z reads set z
+  const int nkeep = order == 2 ? std::min(std::min(c->keep_n, c->keep_want), steps) : 0;
+  c->keep_last = nkeep;
   TRY(upload_xtab(c, s, ptrs.data(), (int64_t)ptrs.size()));
   // device table pointers per step: windows [k][Z][B] and (consecutive steps) first windows [k][Z]
-  std::vector<const float* const*> xstep(steps + 1, nullptr), consec(steps + 1, nullptr);
+  std::vector<const float* const*> xstep(steps + 1, nullptr), consec(steps + 1, nullptr), gc_tab(steps + 1, nullptr);
   for (int k = 0; k <= steps; ++k) {
     TRY(xtab_at(c, (int64_t)k * Z * B, &xstep[k]));
     if (is_consec[k]) TRY(xtab_at(c, nptr + (int64_t)k * Z, &consec[k]));
+    if (is_consec[k] && gc_use) TRY(xtab_at(c, gc_base + (int64_t)k * Z * 2, &gc_tab[k]));
   }
+  // step k's view of the cache (null table: run_gcn computes the step's features itself)
+  auto gc_step = [&](int k, bool sweep = false) {
+    c->gc_cur.sweep = sweep;
+    c->gc_cur.tab = gc_tab[k];
+    c->gc_cur.ent = gc_ent.data();
+    c->gc_cur.w0 = gc_w0.data() + (size_t)k * Z;
+  };
   if (!losses) {
     HIP_TRY(c->scratch_loss.grow((int64_t)(steps + 1) * Z * 4));
     losses = c->scratch_loss.as<float>();
@@ -3008,6 +3265,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     }
     const int slot = steps - 1 - k;
     use_primal(c, slot < nkeep ? slot : SET_MAIN);
+    gc_step(k);
     TRY(run_forward(c, s, c->fast, P, xt, consec[k]));
     if (so) c->so_fc[k] = (int8_t)c->w.fcompact;  // (the layout of so_F slot k, for the sweep)
     TIMED(c, s, C_HEAD, head_fl, launch_head_loss(s, d, c->w, c->fast, P, c->po, xt, 2.f * inv, true));
@@ -3031,6 +3289,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   c->w.F = c->F_main;
   use_primal(c, nkeep > 0 ? SET_QUERY : SET_MAIN);  // slot 0 holds the workspace's own Hs/Cs/Gs
   if (dropout) set_step_drop(c, steps);
+  gc_step(steps);
   TRY(run_forward(c, s, c->fast, P, xq, consec[steps]));
   TIMED(c, s, C_HEAD, head_fl,
         launch_head_loss(s, d, c->w, c->fast, P, c->po, xq, 2.f * inv * query_scale, true));
@@ -3061,6 +3320,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
       use_primal(c, slot < nkeep ? slot : SET_MAIN);
       c->w.primal_kept = slot < nkeep ? 1 : 0;
       if (dropout) set_step_drop(c, k);  // the masks of inner step k's forward
+      gc_step(k, true);
       TRY(run_forward_dual(c, s, th, c->so_u, P, xt, so_F != nullptr, consec[k], c->so_fc[k]));
       TIMED(c, s, C_HEAD, 3.0 * head_fl, launch_head_dual(s, d, c->w, th, c->so_u, P, c->po, xt, 2.f * inv));
       TRY(run_backward_dual(c, s, th, c->so_u, P, c->so_hu));
@@ -3254,6 +3514,7 @@ static int af_prepare(smaml_ctx* c, hipStream_t s, const AdaptCall& a, int64_t n
   HIP_TRY(hipMemsetAsync(f->ggrad, 0, (size_t)Pg * 4, s));
   c->gcn = a.gcn;
   ad_cache_invalidate(c);
+  gc_invalidate(c);  // (the call trains the base in place)
   for (auto& x : c->af_stats) x = 0;
   return SMAML_OK;
 }
@@ -3565,6 +3826,13 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->kn.small_kw = (int)value;
   } else if (k == "gcn_dedup" && (value == 0 || value == 1)) {
     c->kn.gcn_dedup = (int)value;
+  } else if (k == "so_f_store" && (value == 0 || value == 1)) {
+    c->so_f_store = (int)value;
+  } else if (k == "gcn_stream_cache" && (value == 0 || value == 1)) {
+    c->gc_on = (int)value;
+  } else if (k == "gcn_stream_cache_mb" && value >= -1 && value <= (1 << 24)) {
+    c->gc_budget_mb = value;
+    if (value >= 0) gc_drop(c);  // (re-planned under the new cap by the next meta-step)
   } else if (k == "xg_dedup" && (value == 0 || value == 1)) {
     c->kn.xg_dedup = (int)value;
   } else if (k == "wgrad_dedup" && (value == 0 || value == 1)) {

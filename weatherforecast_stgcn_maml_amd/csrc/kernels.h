@@ -101,6 +101,8 @@ enum Variant {
   V_XG_DEDUP,        // k_xg_dedup: layer 0's input projection once per distinct stream row (big-tile forward)
   V_WGRAD_DEDUP,     // layer 0's input-weight gradient over distinct stream rows (k_dg_rowsum + gathered k_wgrad)
   V_F_COMPACT,       // GCN features stored once per distinct stream row (Work::fcompact)
+  V_GCN_CACHE,       // steps whose features came from the per-stream GCN feature cache (no GCN launch once filled)
+  V_GCN_CACHE_ROWS,  // stream rows (N nodes each, either table) the cache computed: a count of rows, not launches
   V_FWD_INFER,       // k_lstm_fwd_infer (smaml_forecast: only h and c kept, in a two-slot ring)
   V_FWD_INFER_DROP,  // k_lstm_fwd_infer_drop (smaml_forecast_ensemble: the same step, grid z = ensemble member)
   NVAR
@@ -465,6 +467,12 @@ struct GcnMlpArgs {
   Drop dr{};
 };
 bool gcn_mlp_supported(const Dims& d);
+// A consecutive-window step's F from the per-stream GCN feature cache: tab [Z][2] (device) holds, per task, its
+// t = 0 table at the first window's stream row w0 and its t >= 1 table at row w0 + 1 (both [.][N][Hc], stream
+// rows one after another). compact: F[z] = the B t = 0 rows, then stream rows w0 + 1 .. w0 + B + T - 2 (XgDedup
+// order); else F[z][t][b N + n] = the row of window b's step t, as k_gcn_mlp / k_gcn_expand lay it out.
+void launch_gcn_cache_gather(hipStream_t s, const Dims& d, int Z, int B, const float* const* tab, float* F,
+                             bool compact);
 // compact: only the distinct rows, F[z][M + (s - 1) N + n] = C[z][s][n] for s >= 1 (XgDedup order)
 void launch_gcn_expand(hipStream_t s, const Dims& d, int Z, int B, const float* C, float* F, bool compact = false);
 int64_t gcn_wimg_bytes(const Dims& d);

@@ -285,6 +285,39 @@ void launch_gcn_expand(hipStream_t s, const Dims& d, int Z, int B, const float* 
   k_gcn_expand<<<dim3(gx, (unsigned)(Z * B * (d.T - 1))), 256, 0, s>>>(C, F, B, d.T, blk);
 }
 
+// Per-stream feature cache -> F (launch_gcn_cache_gather): every segment is one contiguous run of cache rows.
+// compact: blockIdx.y = 2 z + seg (seg 0: the B t = 0 rows; seg 1: the B + T - 2 later stream rows); else
+// blockIdx.y = z T + t, the B N rows of step t.
+__global__ void k_gcn_cache_gather(const float* const* __restrict__ tab, float* __restrict__ F, int B, int T,
+                                   int64_t blk, int compact) {
+  const float* src;
+  float* dst;
+  int64_t n4;
+  if (compact) {
+    const int z = blockIdx.y >> 1, seg = blockIdx.y & 1;
+    src = tab[2 * z + seg];
+    dst = F + ((int64_t)z * T * B + (seg ? B : 0)) * blk;
+    n4 = (int64_t)(seg ? B + T - 2 : B) * blk / 4;
+  } else {
+    const int z = blockIdx.y / T, t = blockIdx.y % T;
+    src = t == 0 ? tab[2 * z] : tab[2 * z + 1] + (int64_t)(t - 1) * blk;
+    dst = F + ((int64_t)z * T + t) * B * blk;
+    n4 = (int64_t)B * blk / 4;
+  }
+  const float4* s4 = reinterpret_cast<const float4*>(src);
+  float4* d4 = reinterpret_cast<float4*>(dst);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    d4[i] = s4[i];
+}
+
+void launch_gcn_cache_gather(hipStream_t s, const Dims& d, int Z, int B, const float* const* tab, float* F,
+                             bool compact) {
+  const int64_t blk = (int64_t)d.N * d.Hc;  // Hc % 4 == 0
+  const int64_t n4 = (int64_t)(compact ? std::max(B, B + d.T - 2) : B) * blk / 4;
+  const unsigned gx = (unsigned)std::min<int64_t>((n4 + 255) / 256, 2048);
+  k_gcn_cache_gather<<<dim3(gx, (unsigned)(Z * (compact ? 2 : d.T))), 256, 0, s>>>(tab, F, B, d.T, blk, compact ? 1 : 0);
+}
+
 bool gcn_mlp_supported(const Dims& d) { return d.Hc == 256 && d.Cin0 <= 32 && d.Cin0 % 4 == 0 && d.T > 1; }
 
 void launch_gcn_mlp(hipStream_t s, const Dims& d, int Zb, int B, const float* const* xtab, const float* gcn,

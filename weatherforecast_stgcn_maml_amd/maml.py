@@ -80,26 +80,46 @@ def stream_len_for(cfg: MamlConfig, dims: ModelDims, support: Optional[int] = No
 KEEP_MARGIN = 8 << 30   # matches api.cpp ensure_keep's free-HBM margin
 
 
-def task_bytes(dims: ModelDims, cfg: MamlConfig, kept: int) -> int:
+def task_bytes(dims: ModelDims, cfg: MamlConfig, kept: int, gcn_cached: bool = False) -> int:
     """Device bytes one task holds in a second-order meta-step (api.cpp reserve /
     ensure_so_store / ensure_keep): workspace [F, gcn ping-pong: 3 Hc; Hs, Cs, Gs and their
-    tangents: 12 L H per row], the per-step GCN feature cache, and ``kept`` inner steps'
-    primal (the last one 5 L H per row: dG + dh; the others 11 L H: Hs, Cs, Gs, dG, dh)."""
+    tangents: 12 L H per row], the per-step GCN feature store, and ``kept`` inner steps'
+    primal (the last one 5 L H per row: dG + dh; the others 11 L H: Hs, Cs, Gs, dG, dh).
+    ``gcn_cached``: the meta-step's features come from the per-stream GCN feature cache
+    (``stream_cache_bytes``), for which ensure_so_store makes no per-step store."""
     rows = cfg.batch * dims.window_size * dims.num_nodes
     Hc, H, L, K = dims.hidden_channels, dims.lstm_hidden_size, dims.lstm_num_layers, cfg.inner_steps
-    f = rows * (3 * Hc + 12 * L * H) + K * rows * Hc
+    f = rows * (3 * Hc + 12 * L * H) + (0 if gcn_cached else K * rows * Hc)
     if kept > 0:
         f += rows * L * H * (5 + 11 * (kept - 1))
     return 4 * f
 
 
-def plan_task_group(dims: ModelDims, cfg: MamlConfig, n_tasks: int, free_bytes: int) -> int:
+def stream_cache_bytes(dims: ModelDims, stream_rows: int) -> int:
+    """Device bytes of one stream's tables in the per-stream GCN feature cache (api.cpp gc_prepare): the
+    features of each of its ``stream_rows`` rows as a window's first row and as a later row. Held for every
+    stream the context has seen, whichever task group is running."""
+    return 4 * 2 * stream_rows * dims.num_nodes * dims.hidden_channels
+
+
+def gcn_cache_applies(cfg: MamlConfig, p_gcn: float) -> bool:
+    """Whether smaml_meta_step serves the default (consecutive) window batches from the per-stream GCN
+    feature cache: a batch of more than one window and no GCN dropout (option ``gcn_stream_cache`` on)."""
+    return cfg.batch > 1 and p_gcn == 0.0
+
+
+def plan_task_group(dims: ModelDims, cfg: MamlConfig, n_tasks: int, free_bytes: int, gcn_cached: bool = False,
+                    stream_rows: int = 0) -> int:
     """Tasks per pass of the C driver for a second-order meta-step: the largest group whose
     workspace fits with EVERY inner step's primal kept (tangent-only sweep), balanced over the
-    groups it implies; all tasks at once when that already fits (or when nothing would)."""
+    groups it implies; all tasks at once when that already fits (or when nothing would).
+    ``gcn_cached``: no per-step feature store per task, and ``n_tasks`` streams of ``stream_rows`` rows in
+    the per-stream cache instead (``task_bytes``, ``stream_cache_bytes``)."""
     if cfg.order != 2 or n_tasks <= 1:
         return n_tasks
-    per = task_bytes(dims, cfg, cfg.inner_steps)
+    per = task_bytes(dims, cfg, cfg.inner_steps, gcn_cached)
+    if gcn_cached:
+        free_bytes -= n_tasks * stream_cache_bytes(dims, stream_rows)
     g = max(1, int((free_bytes - KEEP_MARGIN) // per))
     if g >= n_tasks:
         return n_tasks
@@ -191,7 +211,8 @@ class MetaLearner:
         tg = self.task_group
         if tg == "auto":
             free, _ = torch.cuda.mem_get_info(self.device)
-            tg = plan_task_group(self.dims, self.cfg, len(feats), int(free * self.mem_share))
+            tg = plan_task_group(self.dims, self.cfg, len(feats), int(free * self.mem_share),
+                                 gcn_cache_applies(self.cfg, self.dropout[0]), max(int(f.shape[0]) for f in feats))
         G = min(tg or len(feats), len(feats))
         self._groups = [(z0, feats[z0:z0 + G]) for z0 in range(0, len(feats), G)]
         self.ctx.set_tasks(self._groups[0][1])
