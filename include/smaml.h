@@ -439,6 +439,50 @@ int smaml_meta_step(smaml_ctx* ctx, void* stream, const float* theta, int32_t or
                     int32_t batch, const int32_t* windows_host, float inner_lr, float max_norm,
                     float query_scale, float* meta_grad, float* losses, float* norms, float* fast_out);
 
+/* smaml_meta_step with the GCN base meta-trained too: the same call, plus the base's meta-gradient. The inner
+ * loop is smaml_meta_step's -- every task adapts theta by clip + SGD; the base g is shared by the tasks and is
+ * not adapted per task -- and meta_grad, losses, norms and fast_out are bitwise what smaml_meta_step writes for
+ * the same arguments (one driver; the base work is added after the existing launches of the query step and of
+ * each sweep step).
+ *   gcn_meta_grad [Pg] (device, required, 16-byte aligned; layout of smaml_param_layout(which = 1)): overwritten,
+ *     pads zero: sum over tasks of d(query_scale * L_q(fast_K(theta, g), g)) / dg.
+ *   order 1: the partial derivative at the adapted parameters (fast_K held constant): one base backward on the
+ *     query batch. order 2: the total derivative: each inner step k adds -inner_lr d(g_k . w_k)/dg, g_k that
+ *     step's theta-gradient and w_k the clip-adjusted direction the sweep forms for theta's Hessian product (the
+ *     clip's derivative included). The base has no theta-tangent, so the mixed term is the linear GCN backward
+ *     of the tangent of the layer-0 input gradient, R dF_k = R dG0_k . W_ih0(theta_k) + dG0_k . U_ih0 (U = w_k's
+ *     W_ih0 block), masked by conv4's ReLU derivative, through conv4..conv1 with step k's activations.
+ *     order 0: SMAML_EINVAL.
+ * The base stage runs once per query step and (order 2) once per sweep step, right after that step's backward:
+ * k_lstm_dx0_meta forms the masked layer-0 input gradient of every task in one launch (tangent: one K loop over
+ * [R dG0 | dG0] . [W_ih0 ; U_ih0]), conv1..conv3's outputs are recomputed from the step's windows, and conv4..
+ * conv1 run smaml_gcn_conv_backward's launches per task. Two row forms, chosen per step:
+ *   per-sample: T B N rows per task in smaml_backward_base's sample layout (scattered windows, batch 1,
+ *     p_lstm > 0; every step with option "meta_base_dedup" = 0);
+ *   distinct-row (steps whose tasks read consecutive windows, batch > 1, no dropout; option "meta_base_dedup",
+ *     default 1): the (2B + T - 2) N distinct stream rows per task -- the B N rows of t = 0 as B samples on the
+ *     graph path, stream rows w0 + 1 .. w0 + B + T - 2 as one neighbour-less block -- from the row sums of
+ *     k_dg_rowsum (the ReLU mask and the sum over a stream row's window slots commute). Within tolerance of the
+ *     per-sample form, not bitwise: the summation order differs.
+ * Each task's (and block's) dW, db are written to a slot of their own and added in task order: deterministic
+ * (fixed-order sums), bitwise repeatable. Loss weights and both graph forms compose. p_lstm > 0 is supported
+ * (per-sample form). The stage's buffers are the context's own: they grow only and are freed by smaml_destroy.
+ * Checks: smaml_meta_step's, plus order, gcn_meta_grad and meta_grad (SMAML_EINVAL, before a context is needed);
+ * p_gcn > 0 (smaml_set_dropout): SMAML_ENOTIMPL before anything is allocated or launched. Every buffer is grown
+ * before the first launch: SMAML_ENOMEM leaves all outputs untouched. Does not synchronise the stream. The caller
+ * updates the base and calls smaml_set_gcn_params again (the per-stream feature cache forgets its rows).
+ * Not covered: per-task base adaptation in the inner loop, p_gcn > 0, smaml_adapt_steps_multi with a trained base. */
+int smaml_meta_step_base(smaml_ctx* ctx, void* stream, const float* theta, int32_t order, int32_t steps,
+                         int32_t batch, const int32_t* windows_host, float inner_lr, float max_norm,
+                         float query_scale, float* meta_grad, float* gcn_meta_grad, float* losses, float* norms,
+                         float* fast_out);
+
+/* Host-side counters of the last smaml_meta_step_base call that reached its buffers: [0] base stages run (order
+ * 1: 1, order 2: 1 + steps), [1] of those, stages in the distinct-row form, [2] in the per-sample form, [3]
+ * tangent stages, [4] bytes held by the stage's buffers, [5] rows sent through the GCN backward. Writes
+ * min(cap, count) entries; *count = 6. Measurement and tests only. */
+int smaml_meta_base_stats(const smaml_ctx* ctx, int64_t* counts, int32_t cap, int32_t* count);
+
 /* Outer update (train_hybrid_maml_v5.py:174-179, 245-249): clip_grad_norm_(max_norm) of
  * `grad` then torch.optim.AdamW step `step` (1-based) on theta, m, v (n floats).
  * norm_out (optional, device float): pre-clip norm. */
@@ -522,7 +566,7 @@ int smaml_adapt_phases(const smaml_ctx* ctx, double* ms, int32_t cap, int32_t* c
  * (SMAML_EINVAL); the dims of the LSTM path, the graph and the tasks (SMAML_EINVAL / SMAML_ESTATE); the window
  * range (SMAML_EINVAL). Every buffer is grown before the first launch: SMAML_ENOMEM leaves all six vectors
  * untouched. Deterministic (fixed-order sums); does not synchronise the stream.
- * Not covered: smaml_adapt_steps_multi with a trained base, GCN gradients inside smaml_meta_step. */
+ * Not covered: smaml_adapt_steps_multi with a trained base (the meta-step's base gradient: smaml_meta_step_base). */
 int smaml_adapt_steps_full(smaml_ctx* ctx, void* stream, float* theta, float* m, float* v, float* gcn, float* gcn_m,
                            float* gcn_v, int32_t step0, int32_t nsteps, int32_t batch, const int32_t* windows_host,
                            const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
@@ -566,8 +610,9 @@ int smaml_backward(smaml_ctx* ctx, void* stream, const float* theta, const float
  * activations and gradient buffers (nsamples*T*N rows x (3 Hc + 2 max(Hc, Cin) + Cin) floats, plus the GCNConv
  * backward's scratch) are the context's own: they grow only and are freed by smaml_destroy.
  * smaml_adapt_steps_full runs whole steps of one region with this gradient inside the library.
- * Not covered: GCN gradients inside smaml_meta_step / smaml_adapt_steps_multi, whose feature cache and
- * distinct-row paths assume a frozen base. */
+ * smaml_meta_step_base computes the base's meta-gradient inside the meta-step.
+ * Not covered: per-task base adaptation in the meta-step's inner loop, p_gcn > 0 there, and
+ * smaml_adapt_steps_multi with a trained base. */
 int smaml_backward_base(smaml_ctx* ctx, void* stream, const float* theta, const float* const* x_host, int32_t nsamples,
                         const float* dpred, float* grad, float* gcn_grad, float* const* dx_host);
 

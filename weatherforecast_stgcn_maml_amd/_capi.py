@@ -29,7 +29,7 @@ EXPORTS = (
     "smaml_adapt_steps_full", "smaml_adapt_full_stats", "smaml_forecast_rollout", "smaml_rollout_stats",
     "smaml_forecast_rollout_ensemble", "smaml_rollout_ensemble_stats", "smaml_graph_csr", "smaml_set_graph_weighted",
     "smaml_graph_stats", "smaml_loss_weights_check", "smaml_set_loss_weights", "smaml_set_score_weights",
-    "smaml_loss_stats", "smaml_gcn_cache_invalidate",
+    "smaml_loss_stats", "smaml_gcn_cache_invalidate", "smaml_meta_step_base", "smaml_meta_base_stats",
 )
 ABI_VERSION = 9
 GCN_RELU, GCN_PLAIN = 1, 2  # smaml_gcn_conv_ex / _backward flags
@@ -135,6 +135,10 @@ _SIGS["smaml_adapt_steps_full"] = ([P, P, P, P, P, P, P, P, I32, I32, I32, PI32,
 _SIGS["smaml_adapt_full_stats"] = ([P, PI64, I32, PI32], I32)
 # smaml_adapt_full_stats order (launch counters of the last smaml_adapt_steps_full call)
 ADAPT_FULL_STATS = ("steps", "gcn_keep_fused", "gcn_keep_layer", "gcn_dz_fused", "gcn_dz_composed", "gcn_recompute")
+_SIGS["smaml_meta_step_base"] = ([P, P, P, I32, I32, I32, PI32, F32, F32, F32, P, P, P, P, P], I32)
+_SIGS["smaml_meta_base_stats"] = ([P, PI64, I32, PI32], I32)
+# smaml_meta_base_stats order (counters of the last smaml_meta_step_base call)
+META_BASE_STATS = ("stages", "distinct", "per_sample", "tangent", "bytes", "rows")
 _SIGS["smaml_forecast_rollout"] = ([P, P, P, I32, PI32, I32, I32, I32, I32, PF32, P, P], I32)
 _SIGS["smaml_rollout_stats"] = ([P, PI64, I32, PI32], I32)
 # smaml_rollout_stats order (host counters of the last smaml_forecast_rollout call; a row = one time step of one origin)
@@ -468,6 +472,29 @@ class Context:
             ptr(losses) if losses is not None else None,
             ptr(norms) if norms is not None else None,
             ptr(fast_out) if fast_out is not None else None))
+
+    def meta_step_base(self, stream, theta, order, steps, batch, windows: np.ndarray, inner_lr, max_norm,
+                       query_scale, meta_grad, gcn_meta_grad, losses=None, norms=None, fast_out=None):
+        """``meta_step`` plus the GCN base's meta-gradient ``gcn_meta_grad`` [Pg] (smaml_meta_step_base; order 1
+        or 2). The other outputs are bitwise ``meta_step``'s."""
+        w = np.ascontiguousarray(windows, dtype=np.int32)
+        check(self._L.smaml_meta_step_base(
+            self._h, stream, ptr(theta), int(order), int(steps), int(batch), w.ctypes.data_as(PI32),
+            float(inner_lr), float(max_norm), float(query_scale),
+            ptr(meta_grad) if meta_grad is not None else None,
+            ptr(gcn_meta_grad) if gcn_meta_grad is not None else None,
+            ptr(losses) if losses is not None else None,
+            ptr(norms) if norms is not None else None,
+            ptr(fast_out) if fast_out is not None else None))
+
+    def meta_base_stats(self):
+        """{counter: value} of the last meta_step_base call (host counters, no sync)."""
+        n = len(META_BASE_STATS)
+        buf = (ctypes.c_int64 * n)()
+        cnt = ctypes.c_int32()
+        check(self._L.smaml_meta_base_stats(self._h, buf, n, ctypes.byref(cnt)))
+        assert cnt.value == n, (cnt.value, n)
+        return {name: int(buf[i]) for i, name in enumerate(META_BASE_STATS)}
 
     def adapt_steps(self, stream, theta, m, v, step0, windows: np.ndarray, lr_dev, betas, eps, wd, max_norm,
                     losses):

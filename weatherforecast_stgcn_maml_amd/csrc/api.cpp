@@ -382,6 +382,16 @@ struct smaml_ctx {
   // profiles/adapt_full_bench.log)
   int gcn_dz_fused = 0;
   int64_t af_stats[6] = {};  // smaml_adapt_full_stats: counters of the last smaml_adapt_steps_full call
+  // smaml_meta_step_base's base stage (grows only): the stage's gradient rows [Z][R][Hc], one task's recomputed
+  // conv1..conv3 outputs [3][R][Hc], a gradient buffer [R][Hc] and its windows side by side [R][Cin0] (R = B*T*N),
+  // the row sums S and R S [2][Z][(2B + T - 2) N][4H], the stage's and the call's per-task gradients [2][Z][Pg]
+  HipBuf mb_buf;
+  // smaml_set_option("meta_base_dedup"): consecutive-window steps run the base stage over their distinct stream
+  // rows (1) or over every sample row like the other steps (0). On by default: at config-2 shapes, 2 tasks, K = 5,
+  // B = 32, order 2 the call measured 257.7 ms against 288.3 ms per-sample, outside both spreads (smaml_meta_step:
+  // 217.3 ms; profiles/meta_base_bench.log)
+  int meta_base_dedup = 1;
+  int64_t mb_stats[6] = {};  // smaml_meta_base_stats: counters of the last smaml_meta_step_base call
   const float* gcn = nullptr;
   // Loss weights (smaml_set_loss_weights): lw_sets tables [Hf*N][C] in lw_buf; the set index of each region of
   // the running smaml_adapt_steps_multi call in lw_zset; node weights [N] of the forecast score sums in sw_buf
@@ -1784,16 +1794,21 @@ int gcn_conv_bwd(smaml_ctx* c, hipStream_t s, const float* x, int rows, int rps,
 // g <-> gn. x0: conv1's input [rows][Cin0]. dz_top: k_gcn_dz's scratch, which selects the one-launch form of
 // the layer-to-layer gradient (null: GEMM + gather + mask; bitwise the same). stats (optional): [3] += k_gcn_dz
 // launches, [4] += launches of the composed form. cat: the timing category of the layer-to-layer launches. On
-// return g holds the last gradient written (conv1's input gradient [rows][Cin0] when want_dx0).
+// return g holds the last gradient written (conv1's input gradient [rows][Cin0] when want_dx0). ng: the rows of
+// each sample that aggregate over the graph (default N; 0: a neighbour-less block, A_hat = I, on the composed
+// form: the stream rows past t = 0 of smaml_meta_step_base's distinct-row stage).
 int gcn_backward_chain(smaml_ctx* c, hipStream_t s, const float* x0, float* const h[3], float*& g, float*& gn, int rows,
-                       int rps, const float* gcn, float* grad, bool want_dx0, float* dz_top, int64_t* stats, int cat) {
+                       int rps, const float* gcn, float* grad, bool want_dx0, float* dz_top, int64_t* stats, int cat,
+                       int ng = -1) {
   const Dims& d = c->d;
+  if (ng < 0) ng = d.N;
+  if (ng == 0) dz_top = nullptr;  // (k_gcn_dz gathers every sample's first N rows)
   const float sc = c->w.drop.gcn() ? c->w.drop.sc_gcn : 1.f;
   for (int l = 3; l >= 0; --l) {
     const float* x = l == 0 ? x0 : h[l - 1];
     const float* W = gcn + c->go.w[l];
     const int cin = c->go.cin[l];
-    if (grad) TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, d.N, nullptr, grad, c->go.w[l], c->go.b[l]));
+    if (grad) TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, ng, nullptr, grad, c->go.w[l], c->go.b[l]));
     if (l == 0 && !want_dx0) break;
     if (l > 0 && dz_top) {
       TIMED(c, s, cat, 2.0 * rows * d.Hc * cin,
@@ -1803,7 +1818,7 @@ int gcn_backward_chain(smaml_ctx* c, hipStream_t s, const float* x0, float* cons
       if (c->graph_form == 2) ++c->graph_stats[4];
     } else {
       TIMED(c, s, cat, 2.0 * rows * d.Hc * cin, {
-        TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, d.N, gn, nullptr, 0, 0));
+        TRY(gcn_conv_bwd(c, s, x, rows, rps, cin, W, d.Hc, g, ng, gn, nullptr, 0, 0));
         if (l > 0) launch_drop_relu_grad(s, gn, h[l - 1], (int64_t)rows * d.Hc, sc);
       });
       if (stats) stats[4] += l > 0 ? 3 : 2;
@@ -3151,18 +3166,149 @@ int smaml_forecast_ensemble(smaml_ctx* c, void* stream, const float* theta, int3
   });
 }
 
-int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,
-                    const int32_t* windows_host, float inner_lr, float max_norm, float query_scale,
-                    float* meta_grad, float* losses, float* norms, float* fast_out) {
-  TRY(require_ready(c));
-  TRY(check_lstm_dims(c->dims, "smaml_meta_step"));
-  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
-  TRY(check_loss_weights(c, "smaml_meta_step"));
-  if (!theta || steps < 0 || batch <= 0 || !windows_host) return fail(SMAML_EINVAL, "bad meta_step arguments");
-  if (order < 0 || order > 2) return fail(SMAML_EINVAL, "order must be 0, 1 or 2");
-  if (order >= 1 && !meta_grad) return fail(SMAML_EINVAL, "meta_grad required for order >= 1");
+// One meta-step as its entry point received it (smaml_meta_step; smaml_meta_step_base: gcn_meta_grad set).
+struct MetaCall {
+  const float* theta;
+  int order, steps, batch;
+  const int32_t* windows;
+  float inner_lr, max_norm, query_scale;
+  float *meta_grad, *gcn_meta_grad, *losses, *norms, *fast_out;
+};
+
+// The buffers of smaml_meta_step_base's base stage (mb_buf) for steps of Z tasks and B windows.
+struct MbBufs {
+  float *dz = nullptr, *h[3] = {}, *gn = nullptr, *xcat = nullptr, *S = nullptr, *RS = nullptr;
+  float *part = nullptr, *acc = nullptr;  // [Z][2][Pg] the stage's blocks, [Z][Pg] the call's sum
+  int64_t rows = 0;                       // B*T*N: the rows of a task in the per-sample form (the larger one)
+};
+
+// Every buffer of the base stage before the call's first launch: a failure leaves the outputs untouched.
+static int mb_prepare(smaml_ctx* c, int Z, int B, MbBufs* mb) {
+  const Dims& d = c->d;
+  const int64_t rows = (int64_t)B * d.T * d.N, Pg = c->go.total;
+  if (rows * std::max(d.Hc, 8 * d.H) >= (1ll << 31))
+    return fail(SMAML_EINVAL, "batch too large: B*T*N*max(Hc, 8H) must stay below 2^31");
+  const int64_t hsz = rows * d.Hc, xsz = rows * d.Cin0, ssz = (int64_t)Z * xg_dedup_rows(B, d.T, d.N) * 4 * d.H;
+  const int64_t total = (int64_t)Z * hsz + 4 * hsz + xsz + 2 * ssz + 3 * (int64_t)Z * Pg;
+  if (c->mb_buf.grow(total * 4) != hipSuccess ||
+      c->bw_scratch.grow(2 * rows * std::max(d.Hc, d.Cin0) * 4) != hipSuccess)
+    return fail(SMAML_ENOMEM, "smaml_meta_step_base: hipMalloc of the base stage's buffers failed (nothing was launched)");
+  float* p = c->mb_buf.as<float>();
+  mb->rows = rows;
+  mb->dz = p, p += (int64_t)Z * hsz;
+  for (int l = 0; l < 3; ++l) mb->h[l] = p, p += hsz;
+  mb->gn = p, p += hsz;
+  mb->xcat = p, p += xsz;
+  mb->S = p, p += ssz;
+  mb->RS = p, p += ssz;
+  mb->part = p, p += 2 * (int64_t)Z * Pg;
+  mb->acc = p;
+  for (auto& x : c->mb_stats) x = 0;
+  c->mb_stats[4] = c->mb_buf.cap;
+  return SMAML_OK;
+}
+
+// The base stage of one step of smaml_meta_step_base, right after the step's run_backward (U null) or
+// run_backward_dual (U = the sweep direction): acc[z] += alpha * d(.)/dg of task z, from layer 0's gate gradients
+// (w.dG; tangent: w.RGs too) through W_ih0 (th + z P; tangent: U's block too), conv4's ReLU (the features the
+// step's forward read, w.F) and conv4..conv1 with conv1..conv3's outputs recomputed from the step's windows.
+//   distinct-row form (the step's tasks read consecutive windows, wgrad_dedup_ok, option meta_base_dedup): per
+//     task the B N rows of t = 0 as B samples of N rows on the graph path, then stream rows w0 + 1 .. w0 + B + T - 2
+//     as one neighbour-less block; both are slices of the stream (first[z] = the task's first window), the
+//     gradient rows are k_dg_rowsum's sums (the mask and the sum over a stream row's slots commute).
+//   per-sample form: B samples of T N rows in smaml_backward_base's layout (xt = the step's window table).
+// Each block's dW, db go to a slot of its own; the slots are added in task and block order.
+static int meta_base_stage(smaml_ctx* c, hipStream_t s, const MbBufs& mb, const float* const* xt,
+                           const float* const* first, const float* th, const float* U, float alpha) {
+  const Dims& d = c->d;
+  Work& w = c->w;
+  const int Z = w.Z, B = w.B, M = w.M, G4 = 4 * d.H;
+  const int64_t TM = (int64_t)d.T * M, P = c->po.P, Pg = c->go.total, hz = mb.rows * d.Hc;
+  const bool distinct = c->meta_base_dedup && wgrad_dedup_ok(c);
+  const GraphView gv = graph_view(c);
+  Dx0Meta a;
+  a.W = th + c->po.lay[0].wih;
+  a.U = U ? U + c->po.lay[0].wih : nullptr;
+  a.w_zstride = P;
+  a.F = w.F;
+  a.f_zstride = TM * d.Hc;
+  a.out = mb.dz;
+  a.o_zstride = hz;
+  a.K = G4, a.Hc = d.Hc, a.T = d.T, a.M = M, a.N = d.N;
+  a.mdiv = FastDiv((uint32_t)M), a.ndiv = FastDiv((uint32_t)d.N);
+  a.fcompact = w.fcompact;
+  a.distinct = distinct ? 1 : 0;
+  const int rows1 = d.T > 1 ? (B + d.T - 2) * d.N : 0;  // the stream rows past t = 0 (none at T = 1)
+  if (distinct && d.T > 1) {
+    const int64_t sz = xg_dedup_rows(B, d.T, d.N) * G4;
+    TIMED(c, s, C_DGSUM, 0, launch_dg_rowsum(s, d, w, w.dG, TM * G4, mb.S));
+    if (U) TIMED(c, s, C_DGSUM, 0, launch_dg_rowsum(s, d, w, w.RGs, TM * G4, mb.RS));
+    a.A = mb.S, a.RA = U ? mb.RS : nullptr, a.a_zstride = sz;
+    a.rows = M + rows1;
+  } else {  // every slot row (distinct at T = 1: the t = 0 rows are all there is)
+    a.A = w.dG, a.RA = U ? w.RGs : nullptr, a.a_zstride = TM * G4;
+    a.rows = (int)TM;
+  }
+  TIMED(c, s, C_MISC, 2.0 * Z * a.rows * (U ? 2 : 1) * G4 * d.Hc, launch_lstm_dx0_meta(s, a, Z));
+  // one block of rows: conv1..conv3 recomputed, then conv4 -> conv1 into the block's slot
+  auto block = [&](const float* const* tab, const float* x0, int nsamp, int rps, int ng, int64_t row0) -> int {
+    const int rows = nsamp * rps;
+    float* h[3];
+    for (int l = 0; l < 3; ++l) h[l] = mb.h[l] + row0 * d.Hc;
+    for (int l = 0; l < 3; ++l)
+      TIMED(c, s, C_GCN, 2.0 * rows * c->go.cin[l] * d.Hc,
+            launch_gcn_layer(s, d, l, nsamp, nsamp, l == 0 ? tab : nullptr, l == 0 ? (tab ? nullptr : x0) : h[l - 1], h[l],
+                             false, true, c->gcn + c->go.w[l], c->gcn + c->go.b[l], c->go.cin[l], d.Hc, gv, rps, ng,
+                             nullptr));
+    return SMAML_OK;
+  };
+  for (int z = 0; z < Z; ++z) {
+    float* slot = mb.part + (int64_t)z * 2 * Pg;
+    float *g = mb.dz + (int64_t)z * hz, *gn = mb.gn;
+    int nblk = 1;
+    if (distinct) {
+      const float* x0 = first[z];
+      float* h0[3] = {mb.h[0], mb.h[1], mb.h[2]};
+      TRY(block(nullptr, x0, B, d.N, d.N, 0));
+      TRY(gcn_backward_chain(c, s, x0, h0, g, gn, M, d.N, c->gcn, slot, false, nullptr, nullptr, C_GCN));
+      if (rows1 > 0) {
+        const float* x1 = x0 + (int64_t)d.N * d.Cin0;
+        float* h1[3] = {mb.h[0] + (int64_t)M * d.Hc, mb.h[1] + (int64_t)M * d.Hc, mb.h[2] + (int64_t)M * d.Hc};
+        float *g1 = mb.dz + (int64_t)z * hz + (int64_t)M * d.Hc, *gn1 = mb.gn + (int64_t)M * d.Hc;
+        TRY(block(nullptr, x1, 1, rows1, 0, M));
+        TRY(gcn_backward_chain(c, s, x1, h1, g1, gn1, rows1, rows1, c->gcn, slot + Pg, false, nullptr, nullptr, C_GCN, 0));
+        nblk = 2;
+      }
+      c->mb_stats[5] += M + rows1;
+    } else {
+      const int rps = d.T * d.N;
+      float* h0[3] = {mb.h[0], mb.h[1], mb.h[2]};
+      TIMED(c, s, C_GCN, 0, launch_gather_slabs(s, xt + (int64_t)z * B, B, (int64_t)rps * d.Cin0, mb.xcat));
+      TRY(block(xt + (int64_t)z * B, nullptr, B, rps, d.N, 0));
+      TRY(gcn_backward_chain(c, s, mb.xcat, h0, g, gn, B * rps, rps, c->gcn, slot, false, nullptr, nullptr, C_GCN));
+      c->mb_stats[5] += (int64_t)B * rps;
+    }
+    for (int i = 0; i < nblk; ++i)
+      TIMED(c, s, C_MISC, 0, launch_axpy(s, mb.acc + (int64_t)z * Pg, slot + (int64_t)i * Pg, Pg, alpha));
+  }
+  c->mb_stats[0] += 1;
+  c->mb_stats[distinct ? 1 : 2] += 1;
+  if (U) c->mb_stats[3] += 1;
+  HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+// The meta-step, once: the inner loop, the query step and (order 2) the sweep; with a.gcn_meta_grad the base
+// stage after the query step's backward and after each sweep step's tangent backward. The launches of a call
+// without it are smaml_meta_step's, in its order.
+static int meta_run(smaml_ctx* c, hipStream_t s, const MetaCall& a) {
+  const float* theta = a.theta;
+  const int order = a.order, steps = a.steps, batch = a.batch;
+  const int32_t* windows_host = a.windows;
+  const float inner_lr = a.inner_lr, max_norm = a.max_norm, query_scale = a.query_scale;
+  float *meta_grad = a.meta_grad, *losses = a.losses, *norms = a.norms, *fast_out = a.fast_out;
+  const bool base = a.gcn_meta_grad != nullptr;
   TRY(ensure_device(c));
-  hipStream_t s = (hipStream_t)stream;
   const Dims& d = c->d;
   const int Z = (int)c->feats.size();
   const int B = batch;
@@ -3222,6 +3368,8 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   const bool so_cached = gc_use && std::find(is_consec.begin(), is_consec.begin() + steps, (char)0) == is_consec.begin() + steps;
   if (order == 2) TRY(ensure_so_store(c, std::max(steps, 1), Z, B, so_cached));
   if (order == 2) TRY(ensure_keep(c, steps, Z, B, so_cached));
+  MbBufs mb;
+  if (base) TRY(mb_prepare(c, Z, B, &mb));
   set_work(c, Z, B);
   use_loss_weights(c, nullptr);  // task z reads set z
   const int nkeep = order == 2 ? std::min(std::min(c->keep_n, c->keep_want), steps) : 0;
@@ -3249,6 +3397,11 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   const float inv = 1.f / ((float)d.N * d.HfC * B);
   const bool dropout = c->p_gcn > 0.f || c->p_lstm > 0.f;
   if (dropout) TRY(upload_task_ids(c, s, Z));
+  const int64_t Pg = c->go.total;
+  // (the slots' and the sum's pads are zeroed once per call: every stage overwrites the tensors and leaves the pads)
+  if (base) HIP_TRY(hipMemsetAsync(mb.part, 0, (size_t)(3 * Z * Pg) * 4, s));
+  // each task's first window of step k, as host-side device pointers (the distinct-row form's stream slices)
+  auto first_of = [&](int k) { return ptrs.data() + nptr + (int64_t)k * Z; };
   launch_broadcast(s, theta, P, Z, c->fast);
   const double head_fl = 2.0 * Z * c->w.M * d.HfC * d.H;
   const bool so = order == 2;
@@ -3296,6 +3449,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
   TIMED(c, s, C_MISC, 0, launch_loss_final(s, c->w, inv, losses + (int64_t)steps * Z));
   if (order == 1) {
     TRY(run_backward(c, s, c->fast, P, c->grad));
+    if (base) TRY(meta_base_stage(c, s, mb, xq, first_of(steps), c->fast, nullptr, 1.f));
     TIMED(c, s, C_MISC, 0, launch_sum_tasks(s, c->grad, P, Z, meta_grad));
   } else if (so) {
     // v_K = d(query_scale * L_q)/d theta_K, then back through every inner step:
@@ -3303,6 +3457,7 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     if (fast_out) HIP_TRY(hipMemcpyAsync(fast_out, c->fast, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
     fast_out = nullptr;
     TRY(run_backward(c, s, c->fast, P, c->grad));
+    if (base) TRY(meta_base_stage(c, s, mb, xq, first_of(steps), c->fast, nullptr, 1.f));
     use_primal(c, SET_MAIN);
     float* V = c->grad;
     // w_{K-1}: the clip-adjusted direction of the last inner step at v_K (one kernel: dot + direction)
@@ -3324,6 +3479,8 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
       TRY(run_forward_dual(c, s, th, c->so_u, P, xt, so_F != nullptr, consec[k], c->so_fc[k]));
       TIMED(c, s, C_HEAD, 3.0 * head_fl, launch_head_dual(s, d, c->w, th, c->so_u, P, c->po, xt, 2.f * inv));
       TRY(run_backward_dual(c, s, th, c->so_u, P, c->so_hu));
+      // the mixed term of step k: -lr d(g_k . w_k)/dg, w_k = so_u (still this step's direction)
+      if (base) TRY(meta_base_stage(c, s, mb, xt, first_of(k), th, c->so_u, -inner_lr));
       if (k > 0)  // v_k = v_{k+1} - lr H_k w_k and w_{k-1} (dot g_{k-1} . v_k, direction): one kernel
         TIMED(c, s, C_MISC, 0,
               HIP_TRY(launch_sweep_update(s, V, c->so_hu, -inner_lr, so_grad + (int64_t)(k - 1) * Z * P, P, Z,
@@ -3338,9 +3495,55 @@ int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t orde
     TIMED(c, s, C_MISC, 0, launch_sum_tasks(s, V, P, Z, meta_grad));
     c->w.F = c->F_main;
   }
+  if (base) TIMED(c, s, C_MISC, 0, launch_sum_tasks(s, mb.acc, Pg, Z, a.gcn_meta_grad));
   if (fast_out) HIP_TRY(hipMemcpyAsync(fast_out, c->fast, (size_t)Z * P * 4, hipMemcpyDeviceToDevice, s));
   c->w.drop = Drop{};
   HIP_TRY(hipGetLastError());
+  return SMAML_OK;
+}
+
+int smaml_meta_step(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,
+                    const int32_t* windows_host, float inner_lr, float max_norm, float query_scale,
+                    float* meta_grad, float* losses, float* norms, float* fast_out) {
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_meta_step"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  TRY(check_loss_weights(c, "smaml_meta_step"));
+  if (!theta || steps < 0 || batch <= 0 || !windows_host) return fail(SMAML_EINVAL, "bad meta_step arguments");
+  if (order < 0 || order > 2) return fail(SMAML_EINVAL, "order must be 0, 1 or 2");
+  if (order >= 1 && !meta_grad) return fail(SMAML_EINVAL, "meta_grad required for order >= 1");
+  return meta_run(c, (hipStream_t)stream,
+                  MetaCall{theta, order, steps, batch, windows_host, inner_lr, max_norm, query_scale,
+                           meta_grad, nullptr, losses, norms, fast_out});
+}
+
+int smaml_meta_step_base(smaml_ctx* c, void* stream, const float* theta, int32_t order, int32_t steps, int32_t batch,
+                         const int32_t* windows_host, float inner_lr, float max_norm, float query_scale,
+                         float* meta_grad, float* gcn_meta_grad, float* losses, float* norms, float* fast_out) {
+  // (the checks that need no context first: they run without a device too)
+  if (order != 1 && order != 2)
+    return fail(SMAML_EINVAL, "smaml_meta_step_base: order must be 1 or 2 (order 0 has no meta-gradient), got " +
+                                  std::to_string(order));
+  if (!gcn_meta_grad || !aligned16(gcn_meta_grad))
+    return fail(SMAML_EINVAL, "smaml_meta_step_base: gcn_meta_grad must be a 16-byte aligned device pointer");
+  if (!theta || steps < 0 || batch <= 0 || !windows_host) return fail(SMAML_EINVAL, "bad meta_step_base arguments");
+  if (!meta_grad) return fail(SMAML_EINVAL, "smaml_meta_step_base: meta_grad required");
+  TRY(require_ready(c));
+  TRY(check_lstm_dims(c->dims, "smaml_meta_step_base"));
+  if (c->feats.empty()) return fail(SMAML_ESTATE, "smaml_set_tasks not called");
+  TRY(check_loss_weights(c, "smaml_meta_step_base"));
+  if (c->p_gcn > 0.f)
+    return fail(SMAML_ENOTIMPL, "smaml_meta_step_base: GCN dropout (p_gcn > 0 of smaml_set_dropout) with base "
+                                "gradients is not implemented");
+  return meta_run(c, (hipStream_t)stream,
+                  MetaCall{theta, order, steps, batch, windows_host, inner_lr, max_norm,
+                           query_scale, meta_grad, gcn_meta_grad, losses, norms, fast_out});
+}
+
+int smaml_meta_base_stats(const smaml_ctx* c, int64_t* counts, int32_t cap, int32_t* count) {
+  if (!c || cap < 0 || (cap > 0 && !counts)) return fail(SMAML_EINVAL, "bad meta_base_stats arguments");
+  for (int i = 0; i < 6 && i < cap; ++i) counts[i] = c->mb_stats[i];
+  if (count) *count = 6;
   return SMAML_OK;
 }
 
@@ -3861,6 +4064,8 @@ int smaml_set_option(smaml_ctx* c, const char* key, int64_t value) {
     c->gcn_keep = (int)value;
   } else if (k == "gcn_dz_fused" && (value == 0 || value == 1)) {
     c->gcn_dz_fused = (int)value;
+  } else if (k == "meta_base_dedup" && (value == 0 || value == 1)) {
+    c->meta_base_dedup = (int)value;
   } else if (k == "adapt_gcn_batch" && value >= 0 && value <= 256) {
     c->ad_gcn_batch = (int)value;
   } else if (k == "wgrad_group_wgs" && value >= 1) {

@@ -713,6 +713,24 @@ void launch_gemm_nn_plain(hipStream_t s, const float* A, int rows, int K, const 
 // (k_lstm_dx0: the LSTM's layer-0 input gradient through conv4's ReLU; one task, M = w.M = B*N)
 void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* dG0, const float* Wih0, const float* F,
                      float* dZ);
+// k_lstm_dx0_meta (smaml_meta_step_base): k_lstm_dx0 over the task axis, in the per-sample or the distinct-row
+// (XgDedup order) form, primal (RA, U null) or tangent ([RA | A] . [W ; U], one K loop). Strides in floats.
+struct Dx0Meta {
+  const float* A = nullptr;   // per task [rows][K]: layer 0's dG slab, or its k_dg_rowsum sums (distinct)
+  const float* RA = nullptr;  // the same of the tangent slab, a_zstride apart too; null: primal
+  int64_t a_zstride = 0;
+  const float* W = nullptr;   // W_ih0 of task 0 ([K = 4H][Hc] row-major), w_zstride apart
+  const float* U = nullptr;   // the W_ih0 block of the sweep direction (tangent)
+  int64_t w_zstride = 0;
+  const float* F = nullptr;   // the features the step's forward read, [T][M][Hc] per task or compact (fcompact)
+  int64_t f_zstride = 0;
+  float* out = nullptr;       // per task [rows][Hc]
+  int64_t o_zstride = 0;
+  int rows = 0, K = 0, Hc = 0, T = 0, M = 0, N = 0;
+  int distinct = 0, fcompact = 0;
+  FastDiv mdiv, ndiv;  // by M and by N
+};
+void launch_lstm_dx0_meta(hipStream_t s, const Dx0Meta& a, int Z);
 // The GCN backward's layer-to-layer gradient in one launch (k_gcn_dz) plus one small launch over the t = 0
 // rows (k_gcn_dz_top): out [rows][ncols] = mask_h(A_hat^T (dz [rows][K] . W [K][ncols])), mask_h(x) =
 // h > 0 ? sc x : 0, rows = samples of rps rows whose first N aggregate over the graph (CSR of A_hat^T).

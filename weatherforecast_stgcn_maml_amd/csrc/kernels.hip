@@ -10,6 +10,8 @@
 //   k_wgrad            dW_ih | dW_hh | db  as a split-K GEMM over B*N*T rows
 //   k_lstm_dx0         d loss / d (LSTM layer-0 input) through conv4's ReLU: the step of loss.backward that
 //                      extract_base_features' no_grad (hybrid_model.py:60-78) cuts off (smaml_backward_base)
+//   k_lstm_dx0_meta    k_lstm_dx0 for every task of a meta-step's step, per sample or per distinct stream row,
+//                      primal or tangent (smaml_meta_step_base: the GCN base's meta-gradient)
 //   k_inner_sgd        clip_grad_norm_(1.0) + SGD(lr)   train_hybrid_maml_v5.py:135-139
 //   k_adamw            clip + AdamW (outer)             train_hybrid_maml_v5.py:174-179,245-249
 //
@@ -3228,6 +3230,91 @@ void launch_lstm_dx0(hipStream_t s, const Dims& d, const Work& w, const float* d
   dim3 grid((rows + CfgNN::BM - 1) / CfgNN::BM, (d.Hc + CfgNN::BN - 1) / CfgNN::BN, 1);
   k_lstm_dx0<<<grid, CfgNN::NTH, 0, s>>>(dG0, Wih0, F, dZ, d.T, w.M, d.N, 4 * d.H, d.Hc, FastDiv((uint32_t)w.M),
                                          FastDiv((uint32_t)d.N));
+}
+
+// A operand [rows][w | w]: the concatenation of two row-major [rows][w] matrices along K (w a multiple of 4)
+struct Cat2KC {
+  const float *p0, *p1;
+  int rows, w;
+  __device__ __forceinline__ float4 operator()(int r, int k) const {
+    if (r >= rows || k >= 2 * w) return f4zero();
+    return k < w ? ld4(p0 + (int64_t)r * w + k) : ld4(p1 + (int64_t)r * w + (k - w));
+  }
+};
+// B operand [K | K][cols]: two row-major [K][cols] matrices one below the other
+struct Cat2MC {
+  const float *p0, *p1;
+  int K, cols;
+  __device__ __forceinline__ float4 operator()(int64_t k, int c) const {
+    if (k >= 2 * (int64_t)K || c >= cols) return f4zero();
+    return k < K ? ld4(p0 + k * cols + c) : ld4(p1 + (k - K) * cols + c);
+  }
+};
+
+// k_lstm_dx0 for every task of a meta-step's step in one launch (smaml_meta_step_base), in both row forms, primal
+// and tangent. Task z = blockIdx.z reads its own W_ih0 (W + z wstride) and, tangent, the W_ih0 block of its sweep
+// direction (U + z wstride):
+//   primal:   acc = A . W_ih0                                   K = 4H
+//   tangent:  acc = [R A | A] . [W_ih0 ; U_ih0] = R A . W_ih0 + A . U_ih0    ONE K loop of 8H
+//   out = F > 0 ? acc : 0   (conv4's ReLU derivative; F has no tangent: the base does not depend on theta)
+// per-sample form (distinct 0): A = layer 0's dG slab [T][M][4H] (RA = its tangent), row m = t M + b N + n goes to
+//   k_lstm_dx0's sample layout [b][t N + n]; F's row is m, or, compact features, the distinct row of stream row b + t.
+// distinct-row form (distinct 1): A = k_dg_rowsum's sums in XgDedup order (RA = the sums of the tangent slab), in
+//   and out at the same row r; F's row is r when compact, else WgBGather's mapping to one of the row's slots (a
+//   stream row's features are the same in every window that holds it).
+__global__ __launch_bounds__(NT) void k_lstm_dx0_meta(Dx0Meta a) {
+  __shared__ float smem[CfgNN::SMEM_FLOATS];
+  const int z = blockIdx.z;
+  const float* A = a.A + (int64_t)z * a.a_zstride;
+  const float* W = a.W + (int64_t)z * a.w_zstride;
+  const int m0 = blockIdx.x * CfgNN::BM, n0 = blockIdx.y * CfgNN::BN;
+  Acc<CfgNN> acc;
+  acc.zero();
+  if (a.RA) {
+    Cat2KC la{a.RA + (int64_t)z * a.a_zstride, A, a.rows, a.K};
+    Cat2MC lb{W, a.U + (int64_t)z * a.w_zstride, a.K, a.Hc};
+    gemm_mainloop<CfgNN>(la, lb, m0, n0, 0, 2 * a.K, acc, smem);
+  } else {
+    RowMajorKC la{A, a.rows, a.K};
+    RowMajorMC lb{W, a.K, a.Hc};
+    gemm_mainloop<CfgNN>(la, lb, m0, n0, 0, a.K, acc, smem);
+  }
+  const float* F = a.F + (int64_t)z * a.f_zstride;
+  float* out = a.out + (int64_t)z * a.o_zstride;
+  const int M = a.M, N = a.N, T = a.T;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = m0 + acc_row<CfgNN>(0, r);
+    if (m >= a.rows) continue;
+    int64_t frow = m, orow = m;
+    if (a.distinct) {
+      if (m >= M && !a.fcompact) {  // stream row s -> its slot (t, s - t)
+        const int rr = m - M;
+        const int s1 = (int)a.ndiv.div((uint32_t)rr);
+        const int s = s1 + 1, t = min(s, T - 1);
+        frow = (int64_t)t * M + (int64_t)(s - t) * N + (rr - s1 * N);
+      }
+    } else {
+      const int t = (int)a.mdiv.div((uint32_t)m), q = m - t * M;  // row m = t*M + b*N + n
+      const int b = (int)a.ndiv.div((uint32_t)q), n = q - b * N;
+      orow = ((int64_t)b * T + t) * N + n;
+      if (a.fcompact && t > 0) frow = (int64_t)M + (int64_t)(b + t - 1) * N + n;
+    }
+    const float* f = F + frow * a.Hc;
+    float* o = out + orow * a.Hc;
+#pragma unroll
+    for (int j = 0; j < CfgNN::WTN; ++j) {
+      const int c = n0 + acc_col<CfgNN>(j);
+      if (c < a.Hc) o[c] = f[c] > 0.f ? acc.v[0][j][r] : 0.f;
+    }
+  }
+}
+
+void launch_lstm_dx0_meta(hipStream_t s, const Dx0Meta& a, int Z) {
+  static_assert(CfgNN::WTM == 1, "k_lstm_dx0_meta's epilogue walks one 32-row tile per wave");
+  if (a.rows <= 0 || Z <= 0) return;
+  dim3 grid((a.rows + CfgNN::BM - 1) / CfgNN::BM, (a.Hc + CfgNN::BN - 1) / CfgNN::BN, Z);
+  k_lstm_dx0_meta<<<grid, CfgNN::NTH, 0, s>>>(a);
 }
 
 // The GCN backward's gradient from conv k+1's pre-activation to conv k's (smaml_adapt_steps_full), one GEMM

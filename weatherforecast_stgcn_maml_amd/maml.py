@@ -140,7 +140,8 @@ class MetaLearner:
 
     def __init__(self, dims: ModelDims, cfg: MamlConfig, gcn_params: dict, theta: dict,
                  edge_index: np.ndarray, device=None, process_group=None, task_group="auto",
-                 dropout=(0.0, 0.0), dropout_seed: int = 0, mem_share: float = 1.0, edge_weight=None):
+                 dropout=(0.0, 0.0), dropout_seed: int = 0, mem_share: float = 1.0, edge_weight=None,
+                 train_base: bool = False):
         """``task_group``: tasks batched into one pass of the C driver. ``None`` = all of this
         rank's tasks at once; ``"auto"`` (default) = plan_task_group: second-order meta-steps run
         in groups small enough that every inner step's primal stays resident for the sweep.
@@ -153,7 +154,17 @@ class MetaLearner:
         reference parity setting.
 
         ``mem_share``: the fraction of the device's free HBM the "auto" task-group plan may use (several
-        processes sharing one GPU, e.g. a multi-rank rehearsal on one device, each plan for their share)."""
+        processes sharing one GPU, e.g. a multi-rank rehearsal on one device, each plan for their share).
+
+        ``train_base``: meta-train the GCN base too (``smaml_meta_step_base``; order 1 or 2). The inner loop still
+        adapts ``theta`` alone; the base's meta-gradient rides in the same reduce buffer, and one AdamW step over
+        both vectors clips them jointly (the reference clips an optimiser's parameters jointly). GCN dropout is
+        not supported with it. False (default): the base stays frozen, the same calls and bits as before."""
+        self.train_base = bool(train_base)
+        if self.train_base and float(dropout[0]) > 0.0:
+            raise ValueError("train_base=True does not support GCN dropout (dropout[0] > 0)")
+        if self.train_base and cfg.order not in (1, 2):
+            raise ValueError("train_base=True needs a meta-gradient: cfg.order 1 or 2")
         self.mem_share = float(mem_share)
         self.dims = dims
         self.cfg = cfg
@@ -165,15 +176,23 @@ class MetaLearner:
         # the ELL, or the CSR form for a weighted graph (edge_weight [E]) or an in-degree above 7
         _capi.set_graph_auto(self.ctx, edge_index, edge_weight)
         self.gcn = params.pack(gcn_params, dims, which=1, device=self.device)
-        self.ctx.set_gcn_params(self.gcn)
         self.theta = params.pack(theta, dims, which=0, device=self.device)
         P = self.theta.numel()
-        # ONE collective per meta-step: the meta-gradient and the query-loss sum share a buffer
-        self._reduce = torch.zeros(P + 64, device=self.device)
+        # a trained base lives behind theta in ONE parameter buffer, its meta-gradient behind theta's in the
+        # reduce buffer: one all-reduce and one AdamW launch cover both (both layouts pad to 64 floats, pads zero)
+        Pg = self.gcn.numel() if self.train_base else 0
+        if self.train_base:
+            assert P % 64 == 0 and Pg % 64 == 0, (P, Pg)
+            self._pbuf = torch.cat([self.theta, self.gcn])
+            self.theta, self.gcn = self._pbuf[:P], self._pbuf[P:]
+        self.ctx.set_gcn_params(self.gcn)
+        # ONE collective per meta-step: the meta-gradient(s) and the query-loss sum share a buffer
+        self._reduce = torch.zeros(P + Pg + 64, device=self.device)
         self.meta_grad = self._reduce[:P]
-        self._qsum = self._reduce[P:P + 1]
-        self.m = torch.zeros(P, device=self.device)
-        self.v = torch.zeros(P, device=self.device)
+        self.gcn_meta_grad = self._reduce[P:P + Pg] if self.train_base else None
+        self._qsum = self._reduce[P + Pg:P + Pg + 1]
+        self.m = torch.zeros(P + Pg, device=self.device)
+        self.v = torch.zeros(P + Pg, device=self.device)
         self.step = 0          # outer (AdamW) steps taken
         self.meta_steps = 0    # meta-steps run (any order): keys each meta-step's dropout masks
         self.pg = process_group
@@ -221,6 +240,7 @@ class MetaLearner:
                                   self._loss_w.shape[0] == 1 else self._loss_w[:len(self._groups[0][1])])
         self.ctx.reserve(G, self.cfg.batch)
         self._mg_part = torch.zeros_like(self.meta_grad) if len(self._groups) > 1 else None
+        self._gmg_part = torch.zeros_like(self.gcn_meta_grad) if self.train_base and len(self._groups) > 1 else None
 
     def _upload_loss_weights(self, w):
         """The context's loss table: ``w``, or cleared -- which touches the context only if this learner set one."""
@@ -260,10 +280,15 @@ class MetaLearner:
             self.ctx.set_task_ids(self.task_ids)
             losses = torch.empty(K + 1, Z, device=self.device)
             norms = torch.empty(max(K, 1), Z, device=self.device)
-            self.ctx.meta_step(stream, self.theta, cfg.order, K, cfg.batch, windows, cfg.inner_lr,
-                               cfg.max_norm, cfg.query_loss_scale,
-                               meta_grad=self.meta_grad if cfg.order >= 1 else None,
-                               losses=losses, norms=norms, fast_out=fast_out)
+            if self.train_base:
+                self.ctx.meta_step_base(stream, self.theta, cfg.order, K, cfg.batch, windows, cfg.inner_lr,
+                                        cfg.max_norm, cfg.query_loss_scale, self.meta_grad, self.gcn_meta_grad,
+                                        losses=losses, norms=norms, fast_out=fast_out)
+            else:
+                self.ctx.meta_step(stream, self.theta, cfg.order, K, cfg.batch, windows, cfg.inner_lr,
+                                   cfg.max_norm, cfg.query_loss_scale,
+                                   meta_grad=self.meta_grad if cfg.order >= 1 else None,
+                                   losses=losses, norms=norms, fast_out=fast_out)
         else:
             lparts, nparts = [], []
             for gi, (z0, grp) in enumerate(self._groups):
@@ -275,9 +300,18 @@ class MetaLearner:
                 if self._loss_w is not None and self._loss_w.shape[0] > 1:
                     self._upload_loss_weights(self._loss_w[z0:z0 + n])
                 mg = (self.meta_grad if gi == 0 else self._mg_part) if cfg.order >= 1 else None
-                self.ctx.meta_step(stream, self.theta, cfg.order, K, cfg.batch, windows[:, z0:z0 + n],
-                                   cfg.inner_lr, cfg.max_norm, cfg.query_loss_scale, meta_grad=mg,
-                                   losses=lg, norms=ng, fast_out=fast_out[z0:z0 + n] if fast_out is not None else None)
+                fo = fast_out[z0:z0 + n] if fast_out is not None else None
+                if self.train_base:  # the groups add their base partials as they add meta_grad
+                    gmg = self.gcn_meta_grad if gi == 0 else self._gmg_part
+                    self.ctx.meta_step_base(stream, self.theta, cfg.order, K, cfg.batch, windows[:, z0:z0 + n],
+                                            cfg.inner_lr, cfg.max_norm, cfg.query_loss_scale, mg, gmg,
+                                            losses=lg, norms=ng, fast_out=fo)
+                    if gi > 0:
+                        self.gcn_meta_grad.add_(gmg)
+                else:
+                    self.ctx.meta_step(stream, self.theta, cfg.order, K, cfg.batch, windows[:, z0:z0 + n],
+                                       cfg.inner_lr, cfg.max_norm, cfg.query_loss_scale, meta_grad=mg,
+                                       losses=lg, norms=ng, fast_out=fo)
                 if gi > 0 and mg is not None:
                     self.meta_grad.add_(mg)
                 lparts.append(lg)
@@ -299,9 +333,16 @@ class MetaLearner:
         if cfg.order >= 1:
             self.step += 1
             norm_out = torch.empty(1, device=self.device)
-            self.ctx.adamw_step(stream, self.theta, self.meta_grad, self.m, self.v, self.step,
-                                cfg.outer_lr if lr is None else lr, cfg.outer_betas, cfg.outer_eps, cfg.outer_weight_decay,
-                                cfg.outer_max_norm, norm_out)
+            if self.train_base:  # one launch over [theta | gcn]: clipped jointly, updated together
+                n = self._pbuf.numel()
+                self.ctx.adamw_step(stream, self._pbuf, self._reduce[:n], self.m, self.v, self.step,
+                                    cfg.outer_lr if lr is None else lr, cfg.outer_betas, cfg.outer_eps,
+                                    cfg.outer_weight_decay, cfg.outer_max_norm, norm_out)
+                self.ctx.set_gcn_params(self.gcn)  # the per-stream feature cache forgets its rows
+            else:
+                self.ctx.adamw_step(stream, self.theta, self.meta_grad, self.m, self.v, self.step,
+                                    cfg.outer_lr if lr is None else lr, cfg.outer_betas, cfg.outer_eps, cfg.outer_weight_decay,
+                                    cfg.outer_max_norm, norm_out)
         else:
             norm_out = None
         if not sync:
@@ -322,3 +363,7 @@ class MetaLearner:
 
     def theta_named(self):
         return {k: v.detach().clone() for k, v in params.unpack(self.theta, self.dims, 0).items()}
+
+    def gcn_named(self):
+        """The conv tensors of the base (the trained ones with ``train_base=True``)."""
+        return {k: v.detach().clone() for k, v in params.unpack(self.gcn, self.dims, 1).items()}

@@ -57,14 +57,23 @@ def _task_tables(loss_weights, idx, n):
 def meta_train(dims: ModelDims, features: Sequence, edge_index, gcn_full: dict, theta: dict, cfg: MamlConfig,
                epochs: int = NUM_EPOCHS, batch_tasks: int = BATCH_SIZE, koppen_state: Optional[dict] = None,
                log_csv: Optional[str] = None, ckpt_dir: Optional[str] = None, seed: int = SEED,
-               device: str = "cuda", verbose: bool = True, dropout=(0.0, 0.0), loss_weights=None):
+               device: str = "cuda", verbose: bool = True, dropout=(0.0, 0.0), loss_weights=None,
+               train_base: bool = False):
     """Returns (learner, history). ``gcn_full`` holds every non-trainable hybrid tensor
     (conv params + the unused ``base_stgcn.output_layer``) for the checkpoint. ``dropout`` =
     (STGCN dropout_rate, lstm_dropout): the reference trains with (0.2, 0.2); the default (0, 0)
-    is the parity setting."""
+    is the parity setting. ``train_base``: meta-train the GCN base too (``MetaLearner(train_base=True)``); the
+    checkpoints then hold the trained conv tensors in place of ``gcn_full``'s (the AdamW state saved is theta's)."""
     rng = np.random.RandomState(seed)
     gcn = {k: v for k, v in gcn_full.items() if k.startswith("base_stgcn.conv")}
-    ml = MetaLearner(dims, cfg, gcn, theta, edge_index, device=device, dropout=dropout, dropout_seed=seed)
+    ml = MetaLearner(dims, cfg, gcn, theta, edge_index, device=device, dropout=dropout, dropout_seed=seed,
+                     train_base=train_base)
+    P = ml.theta.numel()
+
+    def gcn_now():  # the checkpoint's non-trainable tensors, the conv ones as trained
+        if not train_base:
+            return gcn_full
+        return {**gcn_full, **{k: v.cpu() for k, v in ml.gcn_named().items()}}
     feats = [f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f)) for f in features]
     feats = [f.to(ml.device, torch.float32).contiguous() for f in feats]
     sched = OuterLR(cfg.outer_lr)
@@ -107,11 +116,11 @@ def meta_train(dims: ModelDims, features: Sequence, edge_index, gcn_full: dict, 
             if ckpt_dir:
                 os.makedirs(ckpt_dir, exist_ok=True)
                 checkpoint.save(checkpoint.meta_checkpoint(
-                    dims, gcn_full, ml.theta, koppen_state, ml.m, ml.v, ml.step, sched.state_dict(), epoch, best,
+                    dims, gcn_now(), ml.theta, koppen_state, ml.m[:P], ml.v[:P], ml.step, sched.state_dict(), epoch, best,
                     lr=sched.lr, initial_lr=cfg.outer_lr), os.path.join(ckpt_dir, "hybrid_maml_model_v5_best.pt"))
     if ckpt_dir:
         checkpoint.save(checkpoint.meta_checkpoint(
-            dims, gcn_full, ml.theta, koppen_state, ml.m, ml.v, ml.step, sched.state_dict(), epochs, best,
+            dims, gcn_now(), ml.theta, koppen_state, ml.m[:P], ml.v[:P], ml.step, sched.state_dict(), epochs, best,
             final_loss=loss, lr=sched.lr, initial_lr=cfg.outer_lr),
             os.path.join(ckpt_dir, "hybrid_maml_model_v5_final.pt"))
     return ml, hist
