@@ -2,7 +2,9 @@
 tasks sharded round-robin over ranks, the meta-step's ONE all-reduce of [meta-gradient |
 query-loss sum], then the replicated clip + AdamW. Two ranks share the test box's one GPU over
 gloo (RCCL needs one GPU per rank; the driver's 8-GPU bench runs the same code over RCCL). Each
-rank is a freshly spawned process (never an exec of a process that touched the GPU)."""
+rank is a freshly spawned process (never an exec of a process that touched the GPU).
+With ``train_base`` the ranks run MetaLearner(train_base=True): the one all-reduce carries
+[meta_grad | gcn_meta_grad | qsum] and the one AdamW covers [theta | gcn]."""
 import os
 import socket
 
@@ -23,13 +25,13 @@ def _free_port():
     return p
 
 
-def _rank_main(rank, world, port, tasks, out_q, config="cfg1"):
+def _rank_main(rank, world, port, tasks, out_q, config="cfg1", train_base=False):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK="0")
     import torch
     import torch.distributed as dist
 
-    from weatherforecast_stgcn_maml_amd import synth
+    from weatherforecast_stgcn_maml_amd import params, synth
     from weatherforecast_stgcn_maml_amd.config import CONFIG1, CONFIG2, MamlConfig
     from weatherforecast_stgcn_maml_amd.distributed import init_from_env, shard_tasks
     from weatherforecast_stgcn_maml_amd.graph import build_spatial_graph
@@ -48,24 +50,33 @@ def _rank_main(rank, world, port, tasks, out_q, config="cfg1"):
     mine = shard_tasks(tasks, rank, world)
     feats = [synth.make_features(synth.task_seed(j), d.num_nodes, stream_len_for(cfg, d)) for j in mine]
     ml = MetaLearner(d, cfg, {k: v for k, v in P.items() if k not in names}, {k: P[k] for k in names}, ei,
-                     device="cuda:0")
+                     device="cuda:0", train_base=train_base)
     ml.set_tasks(feats, task_ids=mine)
-    meta_losses, mg1 = [], None
+    gcn0 = ml.gcn.cpu().numpy().copy()
+    meta_losses, mg1, gmg1 = [], None, None
     for i in range(STEPS):
         meta_losses.append(ml.meta_step().meta_loss)
         if i == 0:  # the first step's all-reduced meta-gradient (both sides at the same theta)
             mg1 = ml.meta_grad.cpu().numpy().copy()
-    out_q.put((rank, mine, ml.theta.cpu().numpy(), meta_losses, mg1))
+            gmg1 = ml.gcn_meta_grad.cpu().numpy().copy() if train_base else None
+    res = (rank, mine, ml.theta.cpu().numpy(), meta_losses, mg1)
+    if train_base:  # + the trained base, its first all-reduced meta-gradient, its initial value, its pad mask
+        lay = torch.zeros_like(ml.gcn, dtype=torch.bool)
+        for k in params.unpack(ml.gcn, d, 1):
+            if k.startswith("base_stgcn.conv"):
+                params.unpack(lay, d, 1)[k][...] = True
+        res += (ml.gcn.cpu().numpy(), gmg1, gcn0, (~lay).cpu().numpy())
+    out_q.put(res)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
 
 
-def _run(world, tasks, config="cfg1"):
+def _run(world, tasks, config="cfg1", train_base=False):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, tasks, q, config)) for r in range(world)]
+    procs = [ctx.Process(target=_rank_main, args=(r, world, port, tasks, q, config, train_base)) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=240) for _ in range(world)], key=lambda t: t[0])
@@ -152,3 +163,33 @@ def test_two_rank_meta_learner_cfg2_shapes():
     err = np.linalg.norm(two[0][4] - one[4]) / np.linalg.norm(one[4])
     assert err <= 1e-6, err
     np.testing.assert_allclose(two[0][3][0], one[3][0], rtol=1e-6)  # (step 1: same theta on both sides)
+
+
+@pytest.mark.parametrize("tasks", [3, 1])
+def test_two_rank_meta_learner_trains_the_base(tasks):
+    """MetaLearner(train_base=True) (smaml_meta_step_base): ONE all-reduce of [meta_grad | gcn_meta_grad | qsum] and
+    ONE AdamW over [theta | gcn]. CONFIG1, order 2, 2 outer steps. tasks = 3: rank 0 holds two tasks, rank 1 one;
+    tasks = 1: rank 1 holds none and joins with zeros of the longer buffer (maml.py Z == 0 path). The criteria of
+    test_two_rank_meta_learner_matches_one_rank, extended to the base."""
+    one = _run(1, tasks, train_base=True)[0]
+    two = _run(2, tasks, train_base=True)
+    assert sorted(two[0][1] + two[1][1]) == list(range(tasks))
+    assert bool(two[1][1]) == (tasks > 1)
+    # across the ranks: theta, gcn, the meta-loss and the all-reduced [meta_grad | gcn_meta_grad], bitwise
+    for i, what in ((2, "theta"), (5, "gcn"), (4, "meta_grad"), (6, "gcn_meta_grad")):
+        assert np.all(np.isfinite(two[0][i])), what
+        assert np.array_equal(two[0][i], two[1][i]), what
+    assert two[0][3] == two[1][3]
+    # against one rank: up to the summation order of the task terms; one task: the same sum, bitwise
+    for i, what in ((2, "theta"), (5, "gcn")):
+        err = np.linalg.norm(two[0][i] - one[i]) / np.linalg.norm(one[i])
+        print(f"tasks {tasks}: {what} two ranks vs one {err:.3g}")
+        assert err <= 1e-6, (what, err)
+        if tasks == 1:
+            assert np.array_equal(two[0][i], one[i]), what
+    np.testing.assert_allclose(two[0][3], one[3], rtol=1e-6)
+    for r in (one, two[0], two[1]):
+        gcn, gmg1, gcn0, pads = r[5], r[6], r[7], r[8]
+        assert not np.array_equal(gcn, gcn0)  # the base moved
+        assert np.any(gmg1[~pads] != 0)
+        assert pads.any() and np.all(gcn[pads] == 0) and np.all(gmg1[pads] == 0)  # and its pads are still 0

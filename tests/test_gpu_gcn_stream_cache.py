@@ -9,15 +9,23 @@ between the t = 0 rows and the later stream rows of a task's compact features in
 Hc = 256 (the fused ``k_gcn_mlp`` fill) or Hc = 16 (the per-layer fill), 3 tasks in task groups of 2 (the cache
 must survive the ``set_tasks`` rotation of every meta-step), two consecutive meta-steps. ``big`` forces the
 bench's kernels as tests/test_gpu_shapes.py does, which is what makes the features compact (``f_compact``).
+
+The last section runs ``smaml_meta_step_base`` the same way (two tasks in one pass, order 2, ``big``): its base stage
+masks by the features as the cache gather laid them out, so ``gcn_meta_grad`` must be bitwise equal too.
 """
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
 
-from weatherforecast_stgcn_maml_amd import synth
+from oracle import refcpu
+from weatherforecast_stgcn_maml_amd import params, synth
 from weatherforecast_stgcn_maml_amd.config import MamlConfig, ModelDims
 from weatherforecast_stgcn_maml_amd.maml import MetaLearner, stream_len_for
 
+import base_meta_oracle as bmo
+import test_gpu_base_meta as bm
 from test_gpu_parity import DEV, grid_edges, split
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +42,7 @@ def edge_weights(ei):
     return np.random.default_rng(5).uniform(0.5, 1.5, ei.shape[1]).astype(np.float32)
 
 
-def learner(hc, order, cache, big, weighted=False, dropout=(0.0, 0.0), batch=B, task_group=2, options=()):
+def learner(hc, order, cache, big, weighted=False, dropout=(0.0, 0.0), batch=B, task_group=2, options=(), tasks=NT):
     d = dims(hc)
     cfg = MamlConfig(inner_steps=K, batch=batch, order=order)
     theta, gcn, _ = split(synth.init_params(31, d, gcn_bias_scale=0.1))
@@ -46,7 +54,7 @@ def learner(hc, order, cache, big, weighted=False, dropout=(0.0, 0.0), batch=B, 
         ml.ctx.set_option(k, v)
     # (B = 3 streams whatever the batch under test: the window tables below index them alike)
     n = stream_len_for(MamlConfig(inner_steps=K, batch=B, order=order), d) + 6
-    ml.set_tasks([synth.make_features(900 + j, d.num_nodes, n) for j in range(NT)])
+    ml.set_tasks([synth.make_features(900 + j, d.num_nodes, n) for j in range(tasks)])
     return ml
 
 
@@ -224,3 +232,89 @@ def test_bypass(case):
     assert_bitwise(a, b, case)
     for _, vc in a:
         assert served(vc) == (0, 0), vc
+
+
+# ----------------------------------------------------------------------------- under smaml_meta_step_base
+BASE_OUT = ("mg", "gmg", "losses", "norms", "fast")
+
+
+def base_learner(hc, cache):
+    """Two tasks in one pass, order 2, the big knobs, the unclipped setting of test_base_meta_cpu.py (inner_lr 0.1,
+    max_norm 10: the sweep's share of the base gradient is well above the tolerance)."""
+    ml = learner(hc, 2, cache, True, task_group=None, tasks=2)
+    ml.cfg = dataclasses.replace(ml.cfg, inner_lr=0.1, max_norm=10.0)
+    return ml
+
+
+def base_calls(ml, n=2, between=None):
+    """`n` smaml_meta_step_base calls on output buffers of their own; per call (outputs, variant counters)."""
+    w = ml.default_windows()
+    out = []
+    for i in range(n):
+        if i and between:
+            between(ml)
+        ml.ctx.variant_counts(reset=True)
+        o, _ = bm.call(ml, w)
+        out.append(({k: o[k].cpu().numpy().copy() for k in BASE_OUT}, ml.ctx.variant_counts()))
+    return out
+
+
+def assert_base_bitwise(a, b, what):
+    for i, ((oa, _), (ob, _)) in enumerate(zip(a, b)):
+        for k in BASE_OUT:
+            assert np.all(np.isfinite(oa[k])), (what, i, k)
+            assert oa[k].tobytes() == ob[k].tobytes(), (what, "call", i, k, float(np.max(np.abs(oa[k] - ob[k]))))
+
+
+@pytest.mark.parametrize("hc", [256, 16])
+def test_base_stage_cached_is_bitwise_the_uncached(hc):
+    """Every inner step served, so no per-step feature store: the base stage masks by ``w.F`` as the cache gather
+    laid it out. All five outputs, ``gcn_meta_grad`` among them, bitwise those of option 0. The first cached call
+    counts every forward and sweep visit (2K + 1) and fills rows, the second fills none; what its ``gcn_layer``
+    category still holds is the base stage's own work, never a fill: per stage (K + 1), task (2) and block (t = 0
+    and the rows past it) conv1..conv3 recomputed (3 launches) and the three layer-to-layer gradients of
+    ``gcn_backward_chain`` (3 timed regions), which carry the same category."""
+    on = base_learner(hc, 1)
+    on.ctx.timing(True)
+    a = base_calls(on, 1)
+    t1 = on.ctx.timing_collect()
+    a += base_calls(on, 1)
+    t2 = on.ctx.timing_collect()
+    off = base_learner(hc, 0)
+    off.ctx.timing(True)
+    b = base_calls(off, 1)
+    u1 = off.ctx.timing_collect()
+    b += base_calls(off, 1)
+    assert_base_bitwise(a, b, f"Hc {hc}")
+    assert served(a[0][1])[0] == 2 * K + 1 and served(a[0][1])[1] > 0, a[0][1]
+    assert served(a[1][1]) == (2 * K + 1, 0), a[1][1]
+    assert served(b[0][1]) == (0, 0) and served(b[1][1]) == (0, 0), (b[0][1], b[1][1])
+    stage = 2 * (K + 1) * 2 * (3 + 3)
+    print(f"Hc {hc}: gcn_layer launches cached {t1['gcn_layer']['launches']} then {t2['gcn_layer']['launches']}, "
+          f"uncached {u1['gcn_layer']['launches']}; the base stage's own {stage}")
+    assert t2["gcn_layer"]["launches"] == stage, t2["gcn_layer"]
+    assert t1["gcn_layer"]["launches"] > stage and u1["gcn_layer"]["launches"] > stage
+    assert not np.array_equal(a[0][0]["gmg"], np.zeros_like(a[0][0]["gmg"]))
+
+
+@pytest.mark.parametrize("hc", [256, 16])
+def test_base_stage_refills_after_new_gcn_values(hc):
+    """The base scaled in place and announced by ``set_gcn_params`` between two calls: the cached arm refills what
+    the first call filled, stays bitwise the uncached arm, and its ``gcn_meta_grad`` meets the float64 oracle at
+    the scaled base (1e-4) -- stale rows would show there."""
+    on, off = base_learner(hc, 1), base_learner(hc, 0)
+    a, b = base_calls(on, between=_changed_gcn), base_calls(off, between=_changed_gcn)
+    assert_base_bitwise(a, b, f"Hc {hc} scaled base")
+    assert a[1][1]["gcn_cache_rows"] == a[0][1]["gcn_cache_rows"] > 0, (a[0][1], a[1][1])
+    assert a[0][0]["gmg"].tobytes() != a[1][0]["gmg"].tobytes()
+    d = on.dims
+    names = list(params.unpack(on.theta, d, 0))
+    Pt = {k: v.cpu().clone() for k, v in params.unpack(on.theta, d, 0).items()}
+    Pg = {k: v.cpu().clone() for k, v in params.unpack(on.gcn, d, 1).items()}  # the scaled values, as the device holds them
+    ei = grid_edges(d)
+    tasks = [refcpu.TaskData(f.cpu().numpy(), ei, d) for f in on.tasks]
+    ref = bmo.meta_step(Pt, Pg, tasks, on.default_windows(), on.cfg.inner_lr, on.cfg.max_norm, 2)
+    got = dict(gmg=torch.from_numpy(a[1][0]["gmg"]), mg=torch.from_numpy(a[1][0]["mg"]),
+               fast=torch.from_numpy(a[1][0]["fast"]), losses=torch.from_numpy(a[1][0]["losses"]))
+    bm.check_base_grad(f"Hc {hc} scaled base", d, got["gmg"], ref)
+    bm.check_theta_part(f"Hc {hc} scaled base", d, names, got, ref)
